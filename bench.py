@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- TALCO-XDrop progressive alignment on MI355X (BASELINE.json metric: DP cells/s + wall-clock to final MSA).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config rnasim10k|rnasim100k|protein5k|rnasim1k_band512]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config rnasim10k|rnasim100k|protein5k|rnasim1k_band512] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line (headline, per-level records of the last pass, roofline from the stored
+static counts and counters).  --full adds the legs that take runs of their own: the single-level peak, the CPU baseline, the wall-clock to the
+final MSA through the CLI, the SURVEY-8d one-pass record and the MSA md5 (--no-peak / --no-cpu / --no-e2e / --no-survey8d drop one of them).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all; see dump_family).
 
 Default workload = the configuration the metric is quoted on: RNASim-shaped 10 000 sequences x 10 kbp, FULL progressive
 alignment over the guide tree (BASELINE.json configs[2]).  One "step" = one complete pass of the hot path over that family:
@@ -74,7 +79,7 @@ def pmc_path(config, workload):
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=3, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default="rnasim10k", choices=sorted(CONFIGS))
     ap.add_argument("--leaves", type=int, default=0, help="override the family size (development)")
@@ -87,7 +92,12 @@ def parse():
     ap.add_argument("--workload", default="calibrated", choices=["calibrated", "survey8d"],
                     help="family parameters: calibrated on the reference's RNASim sample (default), or SURVEY.md 8d as written (per-branch substitution U(0.03, 0.10), "
                          "indel 0.005/site, seed 20260501 + config index)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also run the legs beyond the headline (peak level, CPU baseline, wall-clock to MSA, SURVEY-8d record, MSA md5)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def effective_cpus():
@@ -125,6 +135,21 @@ def write_family(cfg, d):
         for name, s in seqs:
             f.write(f">{name}\n{s}\n")
     return tree, fasta
+
+
+def write_family_child(cfg, d):
+    """Body of the child process that writes the family (forked before the parent imports torch): the seconds it took go into d/ready."""
+    t0 = time.perf_counter()
+    write_family(cfg, d)
+    open(os.path.join(d, "ready"), "w").write(repr(time.perf_counter() - t0))
+
+
+def join_family(gen, d):
+    """Wait for the child that writes the family; the seconds it took."""
+    gen.join()
+    if gen.exitcode != 0:
+        raise RuntimeError(f"writing the family failed (exit code {gen.exitcode})")
+    return float(open(os.path.join(d, "ready")).read())
 
 
 def cpu_baseline(batch, matrix, pk, gpu_paths, gpu_lens, target_seconds=12.0):
@@ -238,7 +263,55 @@ def peak_level(twl, dev, local_rank, cfg, pairs=2048, pool=512, reps=3, warm=1, 
            "workload": f"{pairs} sibling pairs of ~{length}-column profiles (1-8 member sequences per side, weighted counts, PSGP gap penalties), "
                        f"{pool} distinct pairs replicated"}
     k = min(pairs, pool)
-    return out, batch, matrix, pk, aln[:k].cpu().numpy(), alen[:k].cpu().numpy()
+    return out, batch, matrix, pk, aln[:k].cpu().numpy(), alen[:k].cpu().numpy(), err[:k].cpu().numpy()
+
+
+DUMP_BYTES = 64 << 20       # --dump-outputs: all arrays together stay below this
+DUMP_SEED = 20260501
+
+
+def dump_level(d, paths, lens, errs):
+    """--dump-outputs of a single-level configuration: the paths, their lengths and error codes of the last timed launch (every distinct pair;
+    path bytes past a pair's length are not part of its result and are written as 0)."""
+    os.makedirs(d, exist_ok=True)
+    paths = paths.astype(np.float32)
+    paths[np.arange(paths.shape[1])[None, :] >= lens[:, None]] = 0.0
+    np.save(os.path.join(d, "paths.npy"), paths)
+    np.save(os.path.join(d, "path_lengths.npy"), lens.astype(np.float64))
+    np.save(os.path.join(d, "error_codes.npy"), errs.astype(np.float64))
+
+
+def dump_family(d, msa_path, n_rows, aln_len, levels):
+    """The MSA of the last timed pass (the file twl_msa_write makes: FASTA, one line per row, input order) read back once: its md5, and with `d`
+    the arrays of --dump-outputs --
+      msa_rows.npy        a fixed sample of rows (seeded, as many as fit in 3/4 of DUMP_BYTES) as float32 byte codes, [rows, aln_len]
+      msa_row_index.npy   the row numbers (file order) of that sample
+      msa_row_digest.npy  a 52-bit digest of EVERY row (exact in float64): a row outside the sample that differs still shows
+      level_pairs.npy, level_band_cells.npy   pairs and band cells of every level of the pass (twl_msa_report)"""
+    k = int(max(1, min(n_rows, DUMP_BYTES * 3 // 4 // (4 * max(1, aln_len)))))      # (the rest: 8 bytes a row of digests, the level arrays)
+    want = set(np.sort(np.random.default_rng(DUMP_SEED).choice(n_rows, size=k, replace=False)).tolist()) if d else set()
+    md5 = hashlib.md5()
+    rows, index, digest = [], [], []
+    with open(msa_path, "rb") as f:
+        i = 0
+        for line in f:
+            md5.update(line)
+            if line.startswith(b">") or not d:
+                continue
+            seq = line.rstrip(b"\n")
+            digest.append(int.from_bytes(hashlib.blake2b(seq, digest_size=8).digest(), "little") >> 12)
+            if i in want:
+                rows.append(np.frombuffer(seq, dtype=np.uint8).astype(np.float32))
+                index.append(i)
+            i += 1
+    if d:
+        os.makedirs(d, exist_ok=True)
+        np.save(os.path.join(d, "msa_rows.npy"), np.stack(rows) if rows else np.zeros((0, aln_len), np.float32))
+        np.save(os.path.join(d, "msa_row_index.npy"), np.asarray(index, dtype=np.float64))
+        np.save(os.path.join(d, "msa_row_digest.npy"), np.asarray(digest, dtype=np.float64))
+        np.save(os.path.join(d, "level_pairs.npy"), np.asarray([lv.pairs for lv in levels], dtype=np.float64))
+        np.save(os.path.join(d, "level_band_cells.npy"), np.asarray([lv.band_cells for lv in levels], dtype=np.float64))
+    return md5.hexdigest()
 
 
 def wallclock_to_msa(tree, fasta, typ, d):
@@ -337,18 +410,19 @@ def main():
 
     # ---- the workload, built on the host before the GPU is touched: rank 0 writes the family, every rank reads the same files ----
     base = args.keep or os.environ.get("TWL_BENCH_DIR") or os.path.join(tempfile.gettempdir(), f"twl_bench_{os.environ.get('MASTER_PORT', 'solo')}_{os.getppid() if world > 1 else os.getpid()}")
-    tree = fasta = None
+    tree = fasta = gen = None
     gen_s = 0.0
     if family:
         os.makedirs(base, exist_ok=True)
         tree, fasta = os.path.join(base, "t.nwk"), os.path.join(base, "s.fa")
         if rank == 0:
-            t0 = time.perf_counter()
-            tree, fasta = write_family(cfg, base)
-            gen_s = time.perf_counter() - t0
-            open(os.path.join(base, "ready"), "w").write("1")
+            # a forked child writes it while this process imports torch and brings the device up (joined before the first handle is opened)
+            import multiprocessing
+            gen = multiprocessing.get_context("fork").Process(target=write_family_child, args=(cfg, base))
+            gen.start()
     e2e = None
-    if family and world == 1 and not args.no_e2e:
+    if family and world == 1 and args.full and not args.no_e2e:
+        gen_s, gen = join_family(gen, base), None
         try:    # a child process, started before this process touches the GPU
             e2e = wallclock_to_msa(tree, fasta, cfg["type"], base)
         except Exception as ex:  # noqa: BLE001
@@ -368,6 +442,8 @@ def main():
         local_rank = 0
     dev = torch.device(f"cuda:{local_rank}")
     torch.cuda.set_device(dev)
+    if gen is not None:
+        gen_s = join_family(gen, base)
     if world > 1 or os.environ.get("TWL_BENCH_FORCE_SHARD"):
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("MASTER_PORT", "29533")
@@ -458,23 +534,25 @@ def main():
             kernel_ms += tot.kernel_ms
             exch_ms += tot.exchange_ms
         md5 = None
-        if rank == 0:
+        if rank == 0 and (args.full or args.dump_outputs):
             out = os.path.join(base, "bench.aln")
             handles[-1].write(out)
-            md5 = hashlib.md5(open(out, "rb").read()).hexdigest()
+            md5 = dump_family(args.dump_outputs, out, int(tot.n_sequences), int(tot.aln_len), levels)
             os.remove(out)
         for m in handles:
             m.close()
     else:
         # single-level configuration: the step is one launch of the level through twl_align_batch_device
         # (W warm-up launches, then exactly K timed ones between two fences: the batch is generated and uploaded before the clock starts, the paths stay in HBM)
-        peak, pk_batch, matrix, pk, gp, gl = peak_level(twl, dev, local_rank, cfg, reps=max(1, args.steps), warm=max(1, args.warmup), fence=fence)
+        peak, pk_batch, matrix, pk, gp, gl, ge = peak_level(twl, dev, local_rank, cfg, reps=max(1, args.steps), warm=max(1, args.warmup), fence=fence)
         dt = peak["timed_s"]
         cells = peak["band_cells_per_launch"] * args.steps
         nominal_cells = peak["nominal_cells_per_launch"] * args.steps
         kernel_ms = peak["kernel_ms_per_launch"] * args.steps
         exch_ms = 0.0
         levels, tot, md5, open_s = [], None, None, 0.0
+        if rank == 0 and args.dump_outputs:
+            dump_level(args.dump_outputs, gp, gl, ge)
 
     # ranks the collective's communicator holds: the library's own (twl_comm_*) or torch.distributed's RCCL; None when gloo carried the exchange (one-GPU development run)
     rccl_world = 0
@@ -638,22 +716,22 @@ def main():
                     "so it exceeds 1 and measures nothing.  Real HBM traffic (`traffic`, counters) is ~1.1 B per cell, most of it traceback words; compulsory 0.07 B per cell.  "
                     "`issue` = the counters of the profiled run per kernel.  DESIGN.md section 3",
         }
-        if world == 1 and not args.no_peak and family:
+        if world == 1 and args.full and not args.no_peak and family:
             try:
-                peak, pk_batch, matrix, pk, gp, gl = peak_level(twl, dev, local_rank, cfg)
+                peak, pk_batch, matrix, pk, gp, gl, _ = peak_level(twl, dev, local_rank, cfg)
                 out["peak_level"] = peak
             except Exception as e:  # noqa: BLE001
                 out["peak_level"] = {"note": f"failed: {e}"}
-        if world == 1 and not args.no_cpu:
+        if world == 1 and args.full and not args.no_cpu:
             try:
                 if pk_batch is None:
-                    peak2, pk_batch, matrix, pk, gp, gl = peak_level(twl, dev, local_rank, cfg, pairs=64, reps=1)
+                    peak2, pk_batch, matrix, pk, gp, gl, _ = peak_level(twl, dev, local_rank, cfg, pairs=64, reps=1)
                 out["cpu_baseline"] = cpu_baseline(pk_batch, matrix, pk, gp, gl)
             except Exception as e:  # the checker must never take the bench line down
                 out["cpu_baseline"] = {"value": None, "unit": "cells/s", "cores": 0, "kind": "port", "sample": f"failed: {e}"}
         if e2e is not None:
             out["wallclock_to_msa"] = e2e
-        if world == 1 and family and args.config == "rnasim10k" and args.workload == "calibrated" and not args.no_survey8d and not args.leaves and not args.length:
+        if world == 1 and family and args.full and args.config == "rnasim10k" and args.workload == "calibrated" and not args.no_survey8d and not args.leaves and not args.length:
             try:
                 out["survey8d"] = survey8d_record(cfg, local_rank, base)
             except Exception as e:  # noqa: BLE001

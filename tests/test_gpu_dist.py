@@ -140,7 +140,7 @@ def test_bench_with_gpus_2_as_a_plain_command(built, tmp_path):
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--leaves", "400", "--length", "1200",
-                        "--no-cpu", "--no-peak", "--no-e2e", "--no-survey8d"], capture_output=True, text=True, env=env, timeout=800)
+                        "--full", "--no-cpu", "--no-peak", "--no-e2e", "--no-survey8d"], capture_output=True, text=True, env=env, timeout=800)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout
@@ -190,7 +190,7 @@ def test_bench_on_two_gpus_reports_two_ranks_in_the_communicator(built, tmp_path
         env.pop(k, None)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--leaves", "600", "--length", "1500",
-                        "--no-cpu", "--no-peak", "--no-e2e", "--no-survey8d"], capture_output=True, text=True, env=env, timeout=800)
+                        "--full", "--no-cpu", "--no-peak", "--no-e2e", "--no-survey8d"], capture_output=True, text=True, env=env, timeout=800)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.strip()][-1])
     assert line["n_gpus"] == 2 and line["n_ranks_seen_by_rccl"] == 2 and line["config"]["msa_md5"]

@@ -7,7 +7,7 @@ mkdir -p $O
 i=0
 for cfg in "$@"; do
   i=$((i+1))
-  env $cfg python3 $R/bench.py --steps 2 --warmup 1 --no-cpu --no-peak --no-e2e > $O/sweep_$i.json 2> $O/sweep_$i.err
+  env $cfg python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu --no-peak --no-e2e > $O/sweep_$i.json 2> $O/sweep_$i.err
   python3 - "$O/sweep_$i.json" "$cfg" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

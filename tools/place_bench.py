@@ -1,0 +1,91 @@
+"""Placement benchmark (reported, not gated): N_NEW mutated sequences placed into an N_BB-row backbone (`twilight-mi355x -a`), the backbone
+aligned by the product's default mode (-t) from a synthetic family (twilight_amd/synth.py).  Prints one JSON line: the per-phase times of
+the placement as its -v report gives them (count, prepare + DP, restore, collect, finish, read-back, write) and the cells/s of its DP launches.
+
+    python tools/place_bench.py [--new 20000] [--backbone 1000] [--length 10000] [--dir DIR]
+"""
+import argparse
+import json
+import os
+import re
+import subprocess
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+EXE = os.path.join(ROOT, "twilight_amd", "twilight-mi355x")
+
+
+def write_inputs(d, n_bb, n_new, length, seed=20261016):
+    from twilight_amd import synth
+
+    sys.setrecursionlimit(1000000)
+    nwk, leaves = synth.make_family(n_bb, length, seed=seed)
+    tree, fasta, new = os.path.join(d, "bb.nwk"), os.path.join(d, "bb.fa"), os.path.join(d, "new.fa")
+    open(tree, "w").write(nwk + "\n")
+    with open(fasta, "w") as f:
+        for name, s in leaves:
+            f.write(f">{name}\n{s}\n")
+    # the new sequences: leaves of the family mutated once more (substitutions and short indels)
+    rng = np.random.default_rng(seed + 1)
+    lut = np.frombuffer(b"ACGT", dtype=np.uint8)
+    codes = [np.frombuffer(s.encode(), dtype=np.uint8) for _, s in leaves]
+    inv = np.zeros(256, dtype=np.int8)
+    inv[lut] = np.arange(4, dtype=np.int8)
+    with open(new, "wb") as f:
+        for k in range(n_new):
+            src = inv[codes[int(rng.integers(0, n_bb))]]
+            m = synth._mutate(src, rng, 4, 0.01, 0.001, None)
+            f.write(b">q%d\n" % k + lut[m].tobytes() + b"\n")
+    return tree, fasta, new
+
+
+def run(cmd, timeout):
+    t0 = time.perf_counter()
+    r = subprocess.run(["timeout", "-k", "10", str(timeout)] + cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:])
+        raise SystemExit(f"{cmd[0]} exited with {r.returncode}")
+    return r, time.perf_counter() - t0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--new", type=int, default=20000)
+    ap.add_argument("--backbone", type=int, default=1000)
+    ap.add_argument("--length", type=int, default=10000)
+    ap.add_argument("--dir", default=None)
+    a = ap.parse_args()
+    d = a.dir or tempfile.mkdtemp(prefix="place_bench_")
+    os.makedirs(d, exist_ok=True)
+    t0 = time.perf_counter()
+    tree, fasta, new = write_inputs(d, a.backbone, a.new, a.length)
+    t_inputs = time.perf_counter() - t0
+    bb = os.path.join(d, "bb.aln")
+    _, t_bb = run([EXE, "-t", tree, "-i", fasta, "-o", bb], 1200)
+    out = os.path.join(d, "out.aln")
+    r, t_place = run([EXE, "-a", bb, "-i", new, "-o", out, "-v"], 1800)
+    m = re.search(r"Placement phases \(ms\): count ([\d.]+), prepare\+DP ([\d.]+), restore ([\d.]+), collect ([\d.]+), finish ([\d.]+), "
+                  r"read-back ([\d.]+), write ([\d.]+); DP kernel ([\d.]+) ms, (\d+) band cells", r.stderr)
+    w = re.search(r"final alignment length (\d+) \(backbone (\d+)\), (\d+) chunk", r.stderr)
+    if not m or not w:
+        sys.stderr.write(r.stderr[-4000:])
+        raise SystemExit("no phase report in the placement's output")
+    count, dp, restore, collect, finish, read, write, kern = (float(x) for x in m.groups()[:8])
+    cells = int(m.group(9))
+    print(json.dumps({
+        "workload": f"place {a.new} x {a.length} bp into {a.backbone} rows",
+        "backbone_columns": int(w.group(2)), "final_columns": int(w.group(1)), "chunks": int(w.group(3)),
+        "phases_ms": {"count": count, "prepare_dp": dp, "restore": restore, "collect": collect, "finish": finish, "read_back": read, "write": write},
+        "dp_kernel_ms": kern, "band_cells": cells, "dp_cells_per_s": cells / (kern / 1e3) if kern > 0 else None,
+        "dp_cells_per_s_incl_prepare": cells / (dp / 1e3) if dp > 0 else None,
+        "count_collect_finish_over_dp": (count + collect + finish) / dp if dp > 0 else None,
+        "placement_wall_s": round(t_place, 3), "backbone_wall_s": round(t_bb, 3), "inputs_s": round(t_inputs, 3)}))
+
+
+if __name__ == "__main__":
+    main()

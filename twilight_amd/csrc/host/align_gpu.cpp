@@ -285,6 +285,13 @@ twl_params baseParams(Params &param)          // == Talco_xdrop::Params(msa::Par
     return tp;
 }
 
+void nextRetryParams(int16_t err, int32_t minLen, twl_params &tr)
+{
+    if (err == 3) { std::cout << "There might be some bugs in the code!\n"; exit(1); }
+    if (err == 2) tr.flen = std::min(static_cast<int32_t>(tr.flen * 1.2) << 1, minLen);
+    else { tr.xdrop = static_cast<int32_t>(tr.xdrop * 2); tr.flen = std::min(static_cast<int32_t>(tr.xdrop * 4) << 1, minLen); }
+}
+
 // Level staging: the flat arrays of the C ABI ([pair][2][stride][P] etc.), kept for the whole run and only ever grown.  Each
 // pair's profile and gap penalties are built in place in its slot (preparePair), so nothing is copied on the host and the pages
 // are faulted in once, by the threads that fill them.
@@ -428,9 +435,7 @@ void alignmentKernel_GPU(Tree *, NodePairVec &nodes, SequenceDB *database, Optio
             twl_params tr = zeroGapPair(i) ? tz : tp;
             const int minLen = std::min(in[i].lens.first, in[i].lens.second);
             while (errs[i] != 0) {
-                if (errs[i] == 3) { std::cout << "There might be some bugs in the code!\n"; exit(1); }
-                if (errs[i] == 2) tr.flen = std::min(static_cast<int32_t>(tr.flen * 1.2) << 1, minLen);
-                else { tr.xdrop = static_cast<int32_t>(tr.xdrop * 2); tr.flen = std::min(static_cast<int32_t>(tr.xdrop * 4) << 1, minLen); }
+                nextRetryParams(errs[i], minLen, tr);
                 if (option->printDetail) std::cout << "Retry pair No. " << i << "\txdrop " << tr.xdrop << " flen " << tr.flen << '\n';
                 runBatch(ctx, rec, tr, std::vector<int>{i}, in, P, stride, paths, errs);
             }

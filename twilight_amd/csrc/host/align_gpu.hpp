@@ -39,6 +39,12 @@ void exchangeFinalPaths(RunCtx &ctx, twl_store *store, int device, const twl_par
                         LevelRecord &rec);
 const std::vector<int> &selectedDevices();
 twl_params baseParams(Params &param);          // == Talco_xdrop::Params(msa::Params&), TALCO-XDrop.cpp:36-53
+// alignment-cpu.cpp:116-129 (tasks other than 0 retry a failed pair until it passes): the X-drop and band limit of the next attempt after a DP
+// that ended with errorType err (1: xdrop doubles, 2: the band limit grows), minLen = the shorter side after gappy-column removal.
+// errorType 3 ends the run, as it does there.
+void nextRetryParams(int16_t err, int32_t minLen, twl_params &tr);
+// Consensus string and removed-column runs of one side from the column info of twl_level_prepare (letters: "ACGTN" / the 20 acids + 'X').
+void runsAndConsensus(const uint8_t *info, int len, bool removal, const char *letters, IntPairVec &runs, std::string &cons);
 inline double nowMs() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 }  // namespace gpu

@@ -153,6 +153,8 @@ struct PairState {
     stringPair consensus;
 };
 
+}  // namespace
+
 void runsAndConsensus(const uint8_t *info, int len, bool removal, const char *letters, IntPairVec &runs, std::string &cons)
 {
     cons.resize(len);
@@ -165,8 +167,6 @@ void runsAndConsensus(const uint8_t *info, int len, bool removal, const char *le
     }
     if (removal && start >= 0) runs.push_back({start, len - start});
 }
-
-}  // namespace
 
 void uploadSequences(SequenceDB *database, Option *option)
 {
@@ -397,9 +397,7 @@ void alignmentKernel_Resident(Tree *T, NodePairVec &nodes, SequenceDB *database,
                     std::vector<int32_t> len1(n);
                     std::vector<int16_t> err1(n);
                     while (err[i] != 0) {
-                        if (err[i] == 3) { std::cout << "There might be some bugs in the code!\n"; exit(1); }
-                        if (err[i] == 2) tr.flen = std::min(static_cast<int32_t>(tr.flen * 1.2) << 1, minLen);
-                        else { tr.xdrop = static_cast<int32_t>(tr.xdrop * 2); tr.flen = std::min(static_cast<int32_t>(tr.xdrop * 4) << 1, minLen); }
+                        nextRetryParams(err[i], minLen, tr);
                         if (option->printDetail) std::cout << "Retry pair No. " << i << "\txdrop " << tr.xdrop << " flen " << tr.flen << '\n';
                         const double tRetry = nowMs();
                         const int rr = twl_level_align(ctx.stores[d], &tr, one.data(), aln, len1.data(), err1.data());

@@ -30,7 +30,7 @@ static int effectiveCpus()
 
 static bool flag(const char *a, const char *s, const char *l) { return (s && !strcmp(a, s)) || (l && !strcmp(a, l)); }
 
-bool parseCommandLine(int argc, char **argv, Option &o)
+bool parseCommandLine(int argc, char **argv, Option &o, bool allowPlacement)
 {
     bool typeGiven = false;
     o.cpuNum = 0;
@@ -71,11 +71,19 @@ bool parseCommandLine(int argc, char **argv, Option &o)
         else if (flag(a, nullptr, "--test-virtual-devices")) o.testVirtualDevices = std::max(0, atoi(val()));
         else if (flag(a, nullptr, "--test-no-ownership")) o.testNoOwnership = true;
         else if (flag(a, nullptr, "--test-fork-host-staged")) o.testForkHostStaged = true;
+        else if (allowPlacement && flag(a, "-a", "--alignment")) o.backboneAlnFile = val();
+        else if (allowPlacement && flag(a, nullptr, "--test-place-chunk")) o.testPlaceChunk = std::max(0, atoi(val()));
         else if (flag(a, nullptr, "--overwrite")) {}
         else if (flag(a, "-h", "--help")) return false;
         else { std::cerr << "ERROR: unsupported option " << a << " (this build covers the tree+sequences alignment mode only)\n"; exit(1); }
     }
-    if (o.treeFile.empty() || o.seqFile.empty() || o.outFile.empty()) return false;
+    if (!o.backboneAlnFile.empty()) {      // placement (reference option.cpp:15-22): -a -i -o without -t
+        if (!o.treeFile.empty()) { std::cerr << "ERROR: -a together with -t (placement with a tree) is not supported yet.\n"; exit(1); }
+        if (o.seqFile.empty() || o.outFile.empty()) return false;
+        if (o.hostStaged) { std::cerr << "ERROR: --host-staged is not available in placement mode (-a).\n"; exit(1); }
+        if (o.gpuIdx.size() > 1 || o.gpuNum > 1) { std::cerr << "ERROR: placement mode (-a) runs on one GPU: give at most one --gpu-index.\n"; exit(1); }
+        o.alnMode = PLACE_WO_TREE;
+    } else if (o.treeFile.empty() || o.seqFile.empty() || o.outFile.empty()) return false;
     if (o.cpuOnly) {       // the reference's GPU builds route to their CPU kernel here (hip/alignment-gpu.hip.cpp:19-21); this build has no CPU alignment path
         std::cerr << "ERROR: --cpu-only is not available: twilight-mi355x has no CPU alignment path (the CPU checker oracle/e2e_oracle is test infrastructure).\n";
         exit(1);

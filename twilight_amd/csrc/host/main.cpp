@@ -1,5 +1,6 @@
 // twilight_amd/csrc/host/main.cpp -- `twilight-mi355x`: TWILIGHT's tree+sequences mode with the MI355X level kernel.
 //   twilight-mi355x -t tree.nwk -i seqs.fa -o out.aln [-v] [--check] [--gpu-index 0,1,...] [scoring flags as in TWILIGHT]
+//   twilight-mi355x -a backbone.aln -i new.fa -o out.aln [...]   (built with TWL_PLACE: placement without a tree, place.cpp)
 #include "twl_host.hpp"
 
 #include "../../../include/twl_align.h"
@@ -47,11 +48,25 @@ void killAll(const std::vector<pid_t> &kids) { for (pid_t k : kids) if (k > 0) k
 int main(int argc, char **argv)
 {
     msa::Option option;
-    if (!msa::parseCommandLine(argc, argv, option)) {
+#ifdef TWL_PLACE
+    const bool placement = true;
+#else
+    const bool placement = false;
+#endif
+    if (!msa::parseCommandLine(argc, argv, option, placement)) {
         std::cerr << "usage: twilight-mi355x -t <tree.nwk> -i <sequences.fa[.gz]> -o <out.aln> [-r 0.95] [--type n|p] [--match 18 --mismatch -8 --transition -4\n"
                      "        --gap-open -50 --gap-extend -5 --gap-ends X --xdrop 600] [-w] [--rooted] [--filter] [--check] [-v] [--gpu-index 0,1] [--host-staged]\n";
+        if (placement) std::cerr << "       twilight-mi355x -a <backbone.aln[.gz]> -i <new_sequences.fa[.gz]> -o <out.aln> [scoring and filtering flags as above] [--gpu-index 0]\n";
         return 1;
     }
+#ifdef TWL_PLACE
+    if (option.alnMode == msa::PLACE_WO_TREE) {      // one process, one GPU (parseCommandLine refused more)
+        const auto tp = std::chrono::high_resolution_clock::now();
+        const int W = msa::runPlacement(option);
+        std::cerr << "Wrote " << option.outFile << " (length " << W << ") in " << std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - tp).count() << " s\n";
+        return 0;
+    }
+#endif
     auto t0 = std::chrono::high_resolution_clock::now();
     int rank = 0;
     const std::vector<int> allDevices = option.gpuIdx;

@@ -1,0 +1,270 @@
+// twilight_amd/csrc/host/place.cpp -- PLACE_WO_TREE: new sequences placed into an existing alignment, without a tree
+// (reference src/twilight-main.cpp:212-236, `twilight -a backbone.aln -i new.fa -o out.aln`).
+//
+// Every new sequence is aligned, independently, to the profile of the whole backbone (alignment-cpu.cpp with currentTask 2: gapCharScore 0,
+// a failed pair retried until it passes, low-quality sequences neither aligned nor written).  All of it runs on one device:
+//   backbone rows + new sequences -> one store; twl_store_count_columns -> the backbone's profile (readAlignment, io.cpp:200-238)
+//   chunks of new sequences       -> twl_level_prepare / twl_level_align / twl_level_restore, unchanged (include/twl_level.h)
+//   twl_place_collect             -> their final paths kept in HBM, the longest insertion per backbone slot (mergeInsertions)
+//   twl_place_finish              -> every row at the final width (io.cpp:355-449), read back once and written
+// Two deliberate differences from the reference: a backbone row of another length is refused (the reference warns and writes the row at
+// its own width), and the output order is fixed: the backbone rows in file order, then the placed sequences in input order (the reference
+// concatenates its temporary files by shell glob).
+#include "align_gpu.hpp"
+
+#include "../../../include/twl_place.h"
+
+#include <algorithm>
+#include <cstdio>
+#include <fstream>
+#include <iostream>
+#include <numeric>
+#include <string>
+#include <vector>
+
+namespace msa {
+
+using progressive::gpu::baseParams;
+using progressive::gpu::nextRetryParams;
+using progressive::gpu::nowMs;
+using progressive::gpu::runsAndConsensus;
+
+namespace {
+
+[[noreturn]] void die(const char *what, int rc)
+{
+    std::cerr << "ERROR: " << what << " failed (" << rc << "): " << twl_last_error() << '\n';
+    exit(1);
+}
+
+// Device memory one pair of a chunk takes in the level buffers: raw profiles and packed DP columns of both sides (2 * seq_len * (2P + 2)
+// floats), the DP output and the column info.  A chunk gets kChunkBudget of it.
+constexpr double kChunkBudget = 16.0 * (1 << 30);
+constexpr int kMaxChunk = 4096;
+
+struct Totals { double count = 0, dp = 0, restore = 0, collect = 0, finish = 0, read = 0, write = 0, kernel = 0; uint64_t cells = 0; int retries = 0; };
+
+}  // namespace
+
+int runPlacement(Option &option)
+{
+    using progressive::gpu::ensureInit;
+    using progressive::gpu::selectedDevices;
+    Totals tot;
+    Params param(option, option.type);
+
+    // ---- the backbone: every row must have the first row's length ----
+    std::vector<std::string> bbNames, bbRows;
+    io::readRecords(option.backboneAlnFile, [&](std::string &name, std::string &seq) { bbNames.push_back(name); bbRows.push_back(std::move(seq)); });
+    if (bbRows.empty()) { std::cerr << "ERROR: no rows were read from the backbone alignment " << option.backboneAlnFile << ".\n"; exit(1); }
+    const int32_t L = (int32_t)bbRows[0].size();
+    for (size_t k = 1; k < bbRows.size(); ++k)
+        if ((int32_t)bbRows[k].size() != L) {
+            std::cerr << "ERROR: length of \"" << bbNames[k] << "\" (" << bbRows[k].size() << ") does not match in " << option.backboneAlnFile << " (" << L
+                      << "): the rows of a backbone alignment must all have one length.\n";
+            exit(1);
+        }
+    std::cerr << "==== Backbone Alignment ====\nNumber : " << bbRows.size() << "\nLength:  " << L << '\n';
+
+    // ---- new sequences, read and flagged as readSequences does: the "tree" is the star of their names (twilight-main.cpp:214-217) ----
+    SequenceDB database;
+    database.currentTask = 2;
+    Tree *names = new Tree();
+    io::readRecords(option.seqFile, [&](std::string &name, std::string &) {
+        if (names->allNodes.count(name)) return;
+        Node *leaf = new Node(name, 0.0f);
+        leaf->grpID = 0;
+        leaf->weight = 1.0f;
+        names->allNodes[name] = leaf;
+    });
+    io::readSequences(option.seqFile, &database, &option, names);
+    delete names;
+    std::vector<SequenceDB::SequenceInfo *> placed;
+    int lowQ = 0;
+    for (auto *s : database.sequences) { if (s->lowQuality) ++lowQ; else placed.push_back(s); }
+    std::cerr << "Low-quality sequences (not placed): " << lowQ << '\n';
+
+    // ---- one store: backbone rows [0, B), placed sequences [B, B + M) ----
+    ensureInit(&option);
+    const int device = selectedDevices().empty() ? 0 : selectedDevices()[0];
+    const int32_t B = (int32_t)bbRows.size(), M = (int32_t)placed.size();
+    std::vector<const char *> rowPtr;
+    std::vector<int32_t> rowLen;
+    for (auto &r : bbRows) { rowPtr.push_back(r.data()); rowLen.push_back(L); }
+    for (auto *s : placed) { rowPtr.push_back(s->alnStorage[0]); rowLen.push_back(s->len); }
+    twl_store *st = nullptr;
+    int rc = twl_store_create(device, option.type, B + M, rowPtr.data(), rowLen.data(), &st);
+    if (rc != TWL_OK) die("twl_store_create", rc);
+    for (auto &r : bbRows) std::string().swap(r);
+    std::vector<int32_t> bbIds(B);
+    std::iota(bbIds.begin(), bbIds.end(), 0);
+    double t = nowMs();
+    constexpr int32_t kBackboneCache = 0;
+    if ((rc = twl_store_count_columns(st, B, bbIds.data(), kBackboneCache)) != TWL_OK) die("twl_store_count_columns", rc);
+    tot.count = nowMs() - t;
+    twl_place *pl = nullptr;
+    if ((rc = twl_place_create(st, L, &pl)) != TWL_OK) die("twl_place_create", rc);
+
+    // ---- one pair per sequence: reference side = the backbone's cached profile (num = weight = B), query side = the sequence ----
+    const twl_params tp = baseParams(param);
+    twl_params tz = tp;
+    tz.gap_char = 0;                                       // alignment-cpu.cpp:88 (currentTask 2)
+    const bool removal = !(option.gappyVertical == 1.0f);
+    static const char bases[] = {'A', 'C', 'G', 'T', 'N'};
+    static const char acids[] = {'A', 'C', 'D', 'E', 'F', 'G', 'H', 'I', 'K', 'L', 'M', 'N', 'P', 'Q', 'R', 'S', 'T', 'V', 'W', 'Y', 'X'};
+    const char *letters = (option.type == 'n') ? bases : acids;
+    const int P = option.type == 'n' ? 6 : 22;
+
+    // an empty sequence: L reference-only codes (alignment-cpu.cpp:90), straight from the host
+    std::vector<int32_t> todo;                             // store ids of the sequences that go through the DP
+    {
+        std::vector<int32_t> ids, lens;
+        for (int32_t k = 0; k < M; ++k) {
+            if (placed[k]->len == 0) { ids.push_back(B + k); lens.push_back(L); }
+            else todo.push_back(B + k);
+        }
+        if (!ids.empty() && L > 0) {
+            std::vector<int8_t> rows(ids.size() * (size_t)L, 2);
+            t = nowMs();
+            if ((rc = twl_place_collect(pl, st, (int32_t)ids.size(), ids.data(), rows.data(), lens.data(), L, nullptr)) != TWL_OK) die("twl_place_collect", rc);
+            tot.collect += nowMs() - t;
+        }
+    }
+    const auto qlen = [&](int32_t id) { return placed[id - B]->len; };
+
+    // one level of the pairs of `ids`; returns the error code of every pair (those with err != 0 are not collected).  errIn: ONE pair whose
+    // first DP run ended with (*errIn)[0] != 0
+    auto runLevel = [&](const std::vector<int32_t> &ids, const twl_params &prm, std::vector<int16_t> *errIn) {
+        const int32_t n = (int32_t)ids.size();
+        int32_t maxLen = L;
+        for (int32_t id : ids) maxLen = std::max(maxLen, qlen(id));
+        std::vector<twl_side> sides(2 * (size_t)n);
+        std::vector<float> mw((size_t)n, 1.0f);           // seq.weight / groupWeight * num of a lone sequence
+        for (int32_t i = 0; i < n; ++i) {
+            sides[2 * i] = twl_side{0, 0, L, B, (float)B, kBackboneCache, -1, 0};
+            sides[2 * i + 1] = twl_side{1, i, qlen(ids[i]), 1, 1.0f, -1, -1, 0};
+        }
+        std::vector<int32_t> lenOut(2 * (size_t)n), alnLen((size_t)n);
+        std::vector<int16_t> err((size_t)n);
+        double t0 = nowMs();
+        if ((rc = twl_level_prepare(st, &tp, option.gappyVertical, n, sides.data(), ids.data(), mw.data(), maxLen, lenOut.data(), nullptr)) != TWL_OK) die("twl_level_prepare", rc);
+        twl_stats ss{};
+        if (!errIn) {
+            if ((rc = twl_level_align(st, &prm, nullptr, nullptr, alnLen.data(), err.data())) != TWL_OK) die("twl_level_align", rc);
+            if (twl_get_stats(device, &ss) == TWL_OK) { tot.cells += ss.band_cells; tot.kernel += ss.kernel_ms; }
+        } else {
+            // a pair that failed in its chunk (alignment-cpu.cpp:95-128 with currentTask != 0): alone, retried until errorType 0
+            twl_params tr = prm;
+            const int32_t minLen = std::min(lenOut[0], lenOut[1]);
+            err[0] = (*errIn)[0];
+            while (err[0] != 0) {
+                nextRetryParams(err[0], minLen, tr);
+                ++tot.retries;
+                if (option.printDetail) std::cout << "Retry sequence " << placed[ids[0] - B]->name << "\txdrop " << tr.xdrop << " flen " << tr.flen << '\n';
+                if ((rc = twl_level_align(st, &tr, nullptr, nullptr, alnLen.data(), err.data())) != TWL_OK) die("twl_level_align", rc);
+                if (twl_get_stats(device, &ss) == TWL_OK) { tot.cells += ss.band_cells; tot.kernel += ss.kernel_ms; }
+            }
+        }
+        tot.dp += nowMs() - t0;
+        // gappy columns back (alignment-helper.cpp:324-375) for the pairs that lost a column; the others are final as the DP left them
+        t0 = nowMs();
+        const int32_t stride = L + maxLen;
+        std::vector<uint8_t> fromDp((size_t)n, 0);
+        std::vector<int32_t> pathLen((size_t)n, 0), sel;
+        for (int32_t i = 0; i < n; ++i) {
+            if (err[i] != 0) continue;
+            pathLen[i] = alnLen[i];
+            fromDp[i] = 1;
+            if (lenOut[2 * i] < L || lenOut[2 * i + 1] < qlen(ids[i])) sel.push_back(i);
+        }
+        if (!sel.empty()) {
+            std::vector<int32_t> fin(sel.size(), -1);
+            if ((rc = twl_level_restore(st, &tp, (int32_t)sel.size(), sel.data(), stride, fin.data())) != TWL_OK) die("twl_level_restore", rc);
+            std::vector<int32_t> host, hostLen;
+            for (size_t k = 0; k < sel.size(); ++k) {
+                if (fin[k] > 0) { fromDp[sel[k]] = 2; pathLen[sel[k]] = fin[k]; }
+                else { host.push_back(sel[k]); hostLen.push_back(alnLen[sel[k]]); }
+            }
+            if (!host.empty()) {      // (rare: a two-sided run too large for the device) on the host, into the level's path buffer
+                const size_t sl = (size_t)maxLen;
+                std::vector<uint8_t> info(host.size() * 2 * sl);
+                std::vector<int8_t> raw(host.size() * 2 * sl);
+                if ((rc = twl_level_read_colinfo_many(st, (int32_t)host.size(), host.data(), info.data())) != TWL_OK) die("twl_level_read_colinfo_many", rc);
+                if ((rc = twl_level_read_paths(st, (int32_t)host.size(), host.data(), hostLen.data(), raw.data(), (int32_t)(2 * sl))) != TWL_OK) die("twl_level_read_paths", rc);
+                for (size_t k = 0; k < host.size(); ++k) {
+                    const int32_t i = host[k];
+                    std::pair<IntPairVec, IntPairVec> gappy;
+                    stringPair cons;
+                    runsAndConsensus(&info[2 * k * sl], L, removal, letters, gappy.first, cons.first);
+                    runsAndConsensus(&info[(2 * k + 1) * sl], qlen(ids[i]), removal, letters, gappy.second, cons.second);
+                    alnPath path(&raw[2 * k * sl], &raw[2 * k * sl] + hostLen[k]), full;
+                    int alnRef = 0, alnQry = 0;
+                    for (auto a : path) { if (a != 1) ++alnRef; if (a != 2) ++alnQry; }
+                    alignment_helper::addGappyColumnsBack(path, full, gappy, param, {alnRef, alnQry}, cons);
+                    if ((int32_t)full.size() > stride) { std::cerr << "ERROR: path longer than both sides together.\n"; exit(1); }
+                    if ((rc = twl_level_write_final(st, i, full.data(), (int32_t)full.size())) != TWL_OK) die("twl_level_write_final", rc);
+                    fromDp[i] = 2;
+                    pathLen[i] = (int32_t)full.size();
+                }
+            }
+        }
+        tot.restore += nowMs() - t0;
+        t0 = nowMs();
+        if ((rc = twl_place_collect(pl, st, n, ids.data(), nullptr, pathLen.data(), stride, fromDp.data())) != TWL_OK) die("twl_place_collect", rc);
+        tot.collect += nowMs() - t0;
+        return err;
+    };
+
+    // ---- chunks of pairs sized to the device-memory budget (the level buffers of every pair of a 10 kbp input do not fit at once) ----
+    int32_t maxQ = 1;
+    for (int32_t id : todo) maxQ = std::max(maxQ, qlen(id));
+    const double perPair = 2.0 * std::max(L, maxQ) * (2 * P + 2) * sizeof(float) + 4.0 * std::max(L, maxQ);
+    int32_t chunk = (int32_t)std::max(1.0, std::min<double>(kMaxChunk, kChunkBudget / perPair));
+    if (option.testPlaceChunk > 0) chunk = option.testPlaceChunk;
+    int32_t nChunks = 0;
+    for (size_t at = 0; at < todo.size(); at += (size_t)chunk, ++nChunks) {
+        std::vector<int32_t> ids(todo.begin() + at, todo.begin() + std::min(todo.size(), at + (size_t)chunk));
+        std::vector<int16_t> err = runLevel(ids, tz, nullptr);
+        for (size_t i = 0; i < ids.size(); ++i)
+            if (err[i] != 0) {
+                std::vector<int16_t> e1{err[i]};
+                runLevel(std::vector<int32_t>{ids[i]}, tz, &e1);
+            }
+    }
+
+    // ---- merged insertions, final rows, output ----
+    int32_t W = 0;
+    t = nowMs();
+    if ((rc = twl_place_finish(pl, B, bbIds.data(), &W)) != TWL_OK) die("twl_place_finish", rc);
+    tot.finish = nowMs() - t;
+    t = nowMs();
+    std::vector<int32_t> outIds(bbIds);
+    for (int32_t k = 0; k < M; ++k) outIds.push_back(B + k);
+    std::vector<int32_t> outLen(outIds.size());
+    std::vector<char> rows((size_t)outIds.size() * (size_t)W + 1);
+    if ((rc = twl_store_read_rows_of(st, (int32_t)outIds.size(), outIds.data(), rows.data(), outLen.data())) != TWL_OK) die("twl_store_read_rows_of", rc);
+    tot.read = nowMs() - t;
+    twl_place_destroy(pl);
+    twl_store_destroy(st);
+    t = nowMs();
+    {
+        std::ofstream out(option.outFile, std::ios::binary);
+        if (!out) { fprintf(stderr, "ERROR: Failed to open file: %s\n", option.outFile.c_str()); exit(1); }
+        for (size_t k = 0; k < outIds.size(); ++k) {
+            out << '>' << (k < (size_t)B ? bbNames[k] : placed[k - B]->name) << '\n';
+            out.write(&rows[k * (size_t)W], W);
+            out << '\n';
+        }
+        if (!out) { fprintf(stderr, "ERROR: Failed to write file: %s\n", option.outFile.c_str()); exit(1); }
+    }
+    tot.write = nowMs() - t;
+    std::cerr << "Placed " << M << " sequences into " << B << " backbone rows: final alignment length " << W << " (backbone " << L << "), "
+              << nChunks << " chunk(s) of at most " << chunk << ", " << tot.retries << " retried DP run(s)\n";
+    if (option.printDetail)
+        fprintf(stderr, "Placement phases (ms): count %.3f, prepare+DP %.3f, restore %.3f, collect %.3f, finish %.3f, read-back %.3f, write %.3f; "
+                        "DP kernel %.3f ms, %llu band cells\n", tot.count, tot.dp, tot.restore, tot.collect, tot.finish, tot.read, tot.write, tot.kernel,
+                (unsigned long long)tot.cells);
+    return W;
+}
+
+}  // namespace msa

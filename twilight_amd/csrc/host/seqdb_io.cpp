@@ -339,6 +339,17 @@ static bool nextRecord(ChunkReader &in, std::string &carry, std::string &name, s
     }
 }
 
+void readRecords(const std::string &fileName, const std::function<void(std::string &, std::string &)> &each)
+{
+    gzFile f = gzopen(fileName.c_str(), "r");
+    if (!f) { fprintf(stderr, "ERROR: cant open file: %s\n", fileName.c_str()); exit(1); }
+    gzbuffer(f, 1 << 22);
+    ChunkReader in(f);
+    std::string carry, name, seq;
+    while (nextRecord(in, carry, name, seq)) each(name, seq);
+    gzclose(f);
+}
+
 char detectType(const std::string &seqFile)         // option.cpp:115-171: first decisive letter in the first 100 sequence lines
 {
     gzFile f = gzopen(seqFile.c_str(), "r");

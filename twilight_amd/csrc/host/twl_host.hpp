@@ -127,6 +127,8 @@ struct Option {
     bool testNoOwnership = false; // --test-no-ownership: a sharded run deals and exchanges every level (no subtree ownership below a cut)
     int testVirtualDevices = 0;  // --test-virtual-devices n: n replicas of the store on the first device (the several-replica path of the resident kernel on a one-GPU box)
     bool hostStaged = false;     // --host-staged: build profiles on the host and stage them per level (default: device-resident rows)
+    std::string backboneAlnFile; // -a / --alignment: the existing alignment new sequences are placed into (alnMode PLACE_WO_TREE)
+    int testPlaceChunk = 0;      // --test-place-chunk n: placement aligns at most n sequences per level (default: sized to device memory)
     // scoring flags (consumed by Params)
     float match = 18, mismatch = -8, transition = -4, gapOpen = -50, gapExtend = -5, xdrop = 600;
     bool hasGapEnds = false;
@@ -190,6 +192,8 @@ void readSequences(const std::string &fileName, SequenceDB *database, Option *op
 void writeAlignment(const std::string &fileName, SequenceDB *database, int alnLen);
 void writeFinalMSA(SequenceDB *database, Option *option, int alnLen);
 char detectType(const std::string &seqFile);
+// every record of a FASTA(.gz) file, in file order, as readSequences sees them: each(name, sequence)
+void readRecords(const std::string &fileName, const std::function<void(std::string &, std::string &)> &each);
 }  // namespace io
 
 using alnFunction = std::function<void(Tree *, NodePairVec &, SequenceDB *, Option *, Params &)>;
@@ -291,6 +295,10 @@ void downloadRows(SequenceDB *database, Tree *T);
 // atEnd (optional) sees the run's SequenceDB after the output was written and before it is destroyed (the CLI reads the run's totals there)
 int runDefaultAlignment(Option &option, alnFunction kernel, alnFunction deferredKernel, bool writeOutput = true,
                         const std::function<void(SequenceDB *)> &atEnd = nullptr, const std::function<void(SequenceDB *)> &beforeAlign = nullptr);
-bool parseCommandLine(int argc, char **argv, Option &option);
+// allowPlacement: the binary carries the placement mode (twilight-mi355x): -a/--alignment with -i/-o and no -t selects PLACE_WO_TREE
+bool parseCommandLine(int argc, char **argv, Option &option, bool allowPlacement = false);
+// PLACE_WO_TREE (place.cpp, libtwl_host.so): the sequences of option.seqFile placed into the alignment option.backboneAlnFile, written to
+// option.outFile.  Returns the final alignment length.
+int runPlacement(Option &option);
 
 }  // namespace msa

@@ -4,8 +4,10 @@
 // device every entry point fails with TWL_ERR_HIP / TWL_ERR_NOT_INITIALIZED.
 #include "../../include/twl_align.h"
 #include "../../include/twl_level.h"
+#include "../../include/twl_place.h"
 #include "level_kernels.hip.h"
 #include "restore_kernels.hip.h"
+#include "place_kernels.hip.h"
 #include "talco_kernel.hip.h"
 #include "talco_nuc.hip.h"
 #include "talco_global.hip.h"
@@ -1133,3 +1135,4 @@ int twl_get_pair_cells(int device, uint64_t *cells_out, int32_t n)
 }  // extern "C"
 
 #include "twl_level.inc.hip"
+#include "twl_place.inc.hip"

@@ -1,4 +1,4 @@
-"""The launch policy of the nucleotide path (twilight_amd/csrc/twl_align.hip: plan_nucleotide, a pure function of a call's facts) through
+"""The launch policy of the first launch (twilight_amd/csrc/twl_policy.inc.hip: plan_nucleotide and plan_protein, pure functions of a call's facts) through
 twl_plan_describe -- no GPU: which kernel family, matrix mode and window a level of n pairs gets on a 256-CU device."""
 import numpy as np
 import pytest
@@ -74,6 +74,73 @@ def test_a_level_that_outgrew_the_small_window_keeps_the_rest_of_the_pass_off_it
         assert "window 512;" in api.plan_describe(p, _lens(5000, 10000), small_state=-1)
     finally:
         twl.set_knob(api.KNOB_THR_SMALL, 0)
+
+
+PM = synth.protein_matrix()       # 5 x BLOSUM62 (tests/golden/blosum_tables.json holds the table), marker 1024
+MT4 = "tile-parallel on precomputed scores; mode 4; window 1024"
+THR = "throughput, 8 waves x 1 block; mode 3; window 512"
+
+
+# Every expected string restates the protein branch of run_device at commit 4533235 (twilight_amd/csrc/twl_align.hip, the lines named), read as the specification.
+@pytest.mark.parametrize("n,length,expect", [
+    (1, 2000, MT4 + "; 8192000 scores precomputed, corridor 448"),   # 335 few, 345 presim (4000 rows x 2048 floats, 328-330), 374-375 tiles to spread; 363 the corridor knob's default
+    (100, 2000, MT4),
+    (128, 2000, MT4),                                               # 335: few is n <= CUs / 2
+    (129, 2000, MT4),                                               # 344 shared teams would do (presim through sharedSpec, 345) but 374-375 comes first: n <= CUs
+    (200, 2000, MT4),
+    (256, 2000, MT4),
+    (257, 2000, THR),                                               # 344 / 374: n > CUs, no presim -> 383-388
+    (5000, 2000, THR),
+    (4, 300, "speculative teams, 16 waves; mode 4; window 1024"),   # 374: sumLen 600 n < 3 * marker * n -> 377 (2 n <= CUs)
+    (200, 300, "speculative teams, 8 waves x 1 block; mode 4; window 512"),      # 344, 376
+    (300, 300, THR),
+    (128, 40000, "16 waves x 1 block; mode 3; window 1024"),        # 336: 128 x 80000 x 40000 floats > 16 GiB (lengths only) -> 346 mode 3, 389-390
+])
+def test_protein_plan_of_a_level(built, n, length, expect):
+    got = api.plan_describe(twl.make_params(PM), _lens(n, length))
+    assert got.startswith(expect), got
+
+
+def test_protein_plan_depends_on_the_knobs_and_on_the_matrix(built):
+    p = twl.make_params(PM)
+    by_mode = {       # 100 pairs of 2000 columns under every TWL_KNOB_PROT_MODE (307-316, 345, 374-392)
+        "auto": MT4,
+        "dense": "dense, 8 waves x 2 blocks; mode -1; window 1024",             # 316 (statMode stays -1)
+        "sparse": "general (IEEE division); mode 3; window 1024",               # 314 not lean, 345 no presim -> 391-392
+        "presim": "general (IEEE division); mode 4; window 1024",               # 345 presim, 379; 363: no corridor without the lean kernels
+        "r1": "round-1 kernel, 8 waves x 1 block; mode -1; window 512",         # 315
+        "lean_sparse": "16 waves x 1 block; mode 3; window 1024",               # 389-390
+        "lean_presim": "speculative teams, 16 waves; mode 4; window 1024",      # 374 needs auto; 377: 2 n <= CUs
+    }
+    assert set(by_mode) == set(api.PROT_MODES)
+    try:
+        for name, expect in by_mode.items():
+            twl.set_knob(api.KNOB_PROT_MODE, api.PROT_MODES[name])
+            got = api.plan_describe(p, _lens(100, 2000))
+            assert got.startswith(expect), (name, got)
+            if name == "presim":
+                assert got.endswith("corridor 0"), got
+        twl.set_knob(api.KNOB_PROT_MODE, api.PROT_MODES["lean_presim"])
+        assert api.plan_describe(p, _lens(200, 2000)).startswith("16 waves x 1 block on precomputed scores; mode 4; window 1024")      # 378
+        twl.set_knob(api.KNOB_PROT_MODE, api.PROT_MODES["lean_sparse"])
+        assert api.plan_describe(p, _lens(257, 2000)).startswith(THR)                                                                    # 383-388
+    finally:
+        twl.set_knob(api.KNOB_PROT_MODE, 0)
+    twl.set_knob(api.KNOB_NO_SPEC, 1)
+    try:
+        assert api.plan_describe(p, _lens(4, 300)).startswith("16 waves x 1 block on precomputed scores; mode 4; window 1024")          # 377 -> 378
+        assert api.plan_describe(p, _lens(200, 300)).startswith("16 waves x 1 block; mode 3; window 1024")                              # 344 no shared teams -> 345 no presim -> 390
+        assert api.plan_describe(p, _lens(100, 2000)).startswith(MT4)                                                                    # 374 does not ask the knob
+    finally:
+        twl.set_knob(api.KNOB_NO_SPEC, 0)
+    twl.set_knob(api.KNOB_PROT_CORRIDOR, 0)
+    try:
+        assert api.plan_describe(p, _lens(1, 2000)).endswith("corridor 0")                                                               # 363
+    finally:
+        twl.set_knob(api.KNOB_PROT_CORRIDOR, 448)
+    huge = twl.make_params(PM * 4096.0)       # outside the fast division's range (309-313): the round-1 kernels with IEEE division
+    assert api.plan_describe(huge, _lens(10, 2000)).startswith("general (IEEE division); mode 4; window 1024")                          # 345 auto and few -> 379
+    assert api.plan_describe(huge, _lens(300, 2000)).startswith("general (IEEE division); mode 3; window 1024")                         # 392
 
 
 def test_every_knob_the_header_names_is_known_to_the_library_and_to_the_bindings(built):

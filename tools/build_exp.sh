@@ -1,5 +1,6 @@
 #!/bin/bash
 # Cross-compiled variants of libtwl_align.so for the geometry experiments (tools/exp_thr.py, tools/lone_pair_probe.py):
+# The throughput-geometry switch is not in the product source: `git apply tools/exp/thr_geometry.patch` first (tools/exp/README.md).
 #   bash tools/build_exp.sh <name> -DTWL_EXP_THR_W=4 -DTWL_EXP_THR_RPL=2 -DTWL_EXP_THR_MINW=5     ->  build_exp/<name>.so  (+ <name>.resources: registers, scratch, LDS per kernel)
 set -e
 cd "$(dirname "$0")/.."

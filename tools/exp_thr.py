@@ -1,5 +1,6 @@
 """Throughput-geometry experiments: one wide level (2048 pairs x 10 kbp, the bench's peak_level workload) and the leaf-shaped variant on a
-cross-compiled variant of the library (build_exp/*.so).   python tools/exp_thr.py <library.so | base> [pairs] [length] [TWL_KNOB_THR_SMALL]"""
+cross-compiled variant of the library (build_exp/*.so; the -DTWL_EXP_THR_* switch of those builds is tools/exp/thr_geometry.patch, applied
+first: tools/exp/README.md).   python tools/exp_thr.py <library.so | base> [pairs] [length] [TWL_KNOB_THR_SMALL]"""
 import hashlib, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

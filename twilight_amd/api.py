@@ -158,7 +158,7 @@ def set_knob(key: int, value: int):
 
 
 def plan_describe(params, lens, num_cu=256, qry_onehot=False, wide_streak=0, small_state=0) -> str:
-    """twl_plan_describe: the launch plan of a nucleotide call in words (no device needed)."""
+    """twl_plan_describe: the first launch of a nucleotide or protein call in words (no device needed)."""
     wide_streak = int(wide_streak) + (100000 * (32 + int(small_state)) if small_state else 0)      # (1 / -1: the earlier levels of the pass fitted / outgrew the 512-row throughput window)
     lens = np.ascontiguousarray(lens, dtype=np.int32)
     buf = C.create_string_buffer(256)

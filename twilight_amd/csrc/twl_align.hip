@@ -80,6 +80,8 @@ static bool dbg_on() { static const bool v = getenv("TWL_DEBUG") != nullptr; ret
 // Wide path: 8 waves x 9 blocks                   -> 4608-row window (covers flen = 4096), ref columns from L2/HBM.
 // Protein (P = 22): 8 waves x 1 block (512-row window, 96-byte columns in the LDS ring); wide path re-reads both columns per cell.
 
+#include "twl_policy.inc.hip"
+
 struct Buf {
     void *p = nullptr;
     size_t cap = 0;
@@ -116,22 +118,18 @@ struct Device {
     std::vector<uint8_t> gc_zero_host;
     std::vector<int16_t> last_err;                                               // error codes of the last run_device call, as read back by it
     void *probe_h = nullptr; size_t probe_cap = 0;                               // pinned: error codes of a level's sample (run_device, Throughput)
-    bool corridor_lost = false; int corridor_last_n = 0;                         // protein: a pair of an earlier level of this pass left the corridor of the precomputed scores (the later levels score the whole matrix)
-    int small_state = 0, small_last_n = 0;                                       // plan_nucleotide: what the levels of short pairs of this pass found of the 512-row throughput window (1 fits, -1 outgrown), and the pairs of the last such level
+    PassMemory mem;                                                              // what the earlier calls of this pass found (twl_policy.inc.hip)
     int live_stores = 0;                                                         // twl_store handles alive on this device (twl_level.h); guarded by mu
     void *comm = nullptr;                                                        // ncclComm_t of a sharded run (twl_comm_init)
     int comm_world = 0, comm_rank = 0;
     Buf comm_send, comm_recv;                                                    // staging of twl_comm_all_gather_host
-    int wide_streak = 0;                                                         // consecutive small calls whose pairs all outgrew the fast window (run_device: wideFirst)
-    int last_wide_pct = 0, wide_calls = 0;                                       // share of the last narrow-first call's pairs that went on to the wide window; calls started wide since
     int mt_launch = 0;                                                           // launches of the tile-parallel level in flight (work counter index)
     char kname[160] = {0};                                                       // the kernel of the first DP launch of the call in flight
     Buf h2d_freq, h2d_gop, h2d_gex, h2d_len, h2d_num, d_aln, d_alnlen, d_err;   // staging for the host form
     twl_stats stats{};
     std::vector<uint64_t> pair_cells;
     twl::FillArgs fills{};                                                        // byte fills queued for ONE launch in front of the next kernel (queue_fill / flush_fills)
-    char *res_h = nullptr;                                                       // pinned host block the results of a call come back in (collect_kernel writes it)
-    size_t res_cap = 0;
+    char *res_h = nullptr; size_t res_cap = 0;                                   // pinned host block the results of a call come back in (collect_kernel writes it)
     std::vector<int32_t> last_alnlen;                                            // path lengths of the last run_device call, as read back by it
     std::mutex mu;
 };
@@ -182,511 +180,7 @@ int check_params(const twl_params *p)
 
 #include "twl_knobs.inc.hip"
 #include "twl_launch.inc.hip"
-
-#include "twl_policy.inc.hip"
-
-
-// Device-resident core.  len/num are needed on the host for cost ordering (they are tiny).
-int run_device(Device *d, hipStream_t st, const twl_params *p, int32_t n_pairs, int32_t seq_len, const float *d_freq,
-               const float *d_gop, const float *d_gex, const int32_t *d_len, const int32_t *d_num, int8_t *d_aln,
-               int32_t *d_alnlen, int16_t *d_err, const int32_t *h_len, const float *d_packed = nullptr, bool qry_onehot = false,
-               const uint8_t *h_gc_zero = nullptr, int shape = 0)
-{
-    // h_gc_zero: optional [n_pairs], 1 = the pair's gapCharScore is 0 whatever p->gap_char says (the reference decides it per pair,
-    // alignment-cpu.cpp:88; one launch then takes the pairs of both kinds -- the top levels of a 100 000-leaf tree hold a few of each)
-    // shape: what the caller knows about EVERY pair that runs: 2 = single sequences on both sides (no gap letters, denominators of 1): the throughput kernels
-    // then run a step without the per-block tests (talco_lean_kernel, SP 1)
-    // qry_onehot: every query row of every pair of this call has at most one non-zero letter (single sequences: the device-resident
-    // level path knows, it built the profiles) -- the nucleotide kernels then take the four-product form of the column score
-    // d_packed: the level's columns already in the packed [P+2] layout (device-resident level path); no packing pass then
-    HIP_TRY(hipSetDevice(d->id));
-    d->stats = twl_stats{};
-    d->kname[0] = 0;
-    d->fills.n = 0;
-    d->last_err.clear();
-    d->last_alnlen.clear();
-    d->pair_cells.assign((size_t)n_pairs, 0);
-    if (n_pairs == 0) return TWL_OK;
-
-    int rc;
-    const size_t n_cols = (size_t)n_pairs * 2 * (size_t)seq_len;
-    const bool prot = (p->P == 22);
-    if (!d_packed && (rc = d->cols.ensure(n_cols * (size_t)(p->P + 2) * sizeof(float)))) return rc;
-    if ((rc = d->cells.ensure((size_t)n_pairs * sizeof(unsigned long long)))) return rc;
-    if ((rc = d->queue.ensure(64))) return rc;
-    if ((rc = d->items.ensure((size_t)n_pairs * sizeof(int32_t)))) return rc;
-
-    // cost order: longest first (LPT) so the persistent workgroups finish together
-    std::vector<int32_t> len_host;
-    if (!h_len) {
-        len_host.resize((size_t)n_pairs * 2);
-        HIP_TRY(hipMemcpyAsync(len_host.data(), d_len, len_host.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        h_len = len_host.data();
-    }
-    std::vector<int32_t> order((size_t)n_pairs);
-    std::iota(order.begin(), order.end(), 0);
-    // (pairs with an empty side -- masked out by the caller, or really empty -- come last and are not launched at all: what the geometry
-    // is chosen by is the number of pairs that run, e.g. a rank's share of a level)
-    auto live = [&](int32_t x) { return h_len[2 * x] > 0 && h_len[2 * x + 1] > 0; };
-    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) {
-        if (live(x) != live(y)) return live(x);
-        return (int64_t)h_len[2 * x] + h_len[2 * x + 1] > (int64_t)h_len[2 * y] + h_len[2 * y + 1];
-    });
-    int32_t n_run = 0;
-    for (int32_t n = 0; n < n_pairs; ++n) n_run += live(n) ? 1 : 0;
-    uint64_t nominal = 0;
-    for (int32_t n = 0; n < n_pairs; ++n) nominal += (uint64_t)std::max(0, h_len[2 * n]) * (uint64_t)std::max(0, h_len[2 * n + 1]);
-    HIP_TRY(hipMemcpyAsync(d->items.p, order.data(), order.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-
-    TRACE("run_device n_pairs=%d seq_len=%d", n_pairs, seq_len);
-    HIP_TRY(hipEventRecord(d->ev[0], st));
-    if (!d_packed) {
-        const int threads = 256;
-        const int blocks = (int)std::min<size_t>((n_cols + threads - 1) / threads, (size_t)d->num_cu * 8);
-        if (prot) hipLaunchKernelGGL(twl::pack_kernel<22>, dim3(std::max(blocks, 1)), dim3(threads), 0, st, d_freq, d_gop, d_gex, (float *)d->cols.p, n_cols);
-        else hipLaunchKernelGGL(twl::pack_kernel<6>, dim3(std::max(blocks, 1)), dim3(threads), 0, st, d_freq, d_gop, d_gex, (float *)d->cols.p, n_cols);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipEventRecord(d->ev[1], st));
-    if (dbg_on()) { HIP_TRY(hipStreamSynchronize(st)); TRACE("pack done"); }
-
-    twl::KArgs a{};
-    a.cols = d_packed ? d_packed : (const float *)d->cols.p;
-    a.len = d_len; a.num = d_num;
-    a.aln = d_aln; a.aln_len = d_alnlen; a.err = d_err;
-    a.cells = (unsigned long long *)d->cells.p;
-    a.queue = (int32_t *)d->queue.p;
-    a.seq_len = seq_len;
-    a.n_pairs_total = n_pairs;
-    a.gap_open = p->gap_open; a.gap_extend = p->gap_extend; a.gap_char = p->gap_char;
-    a.gc_zero = nullptr;
-    if (h_gc_zero && p->gap_char != 0.0f && std::any_of(h_gc_zero, h_gc_zero + n_pairs, [](uint8_t z) { return z != 0; })) {
-        if ((rc = d->gc_zero.ensure((size_t)n_pairs))) return rc;
-        d->gc_zero_host.assign(h_gc_zero, h_gc_zero + n_pairs);       // (kept with the device: the upload is asynchronous)
-        HIP_TRY(hipMemcpyAsync(d->gc_zero.p, d->gc_zero_host.data(), (size_t)n_pairs, hipMemcpyHostToDevice, st));
-        a.gc_zero = (const uint8_t *)d->gc_zero.p;
-    }
-    a.xdrop = p->xdrop; a.flen = p->flen; a.marker = p->marker;
-    a.step_slack = 1 << 16;
-    const bool want_dbg = dbg_on();
-    a.dbg = nullptr;
-    if (want_dbg) {
-        if ((rc = d->dbg.ensure((size_t)n_pairs * 16 * sizeof(int32_t) + 2048 + 16 * 192 * 32))) return rc;     // per-pair records, then the stamp build's sums and timeline
-        HIP_TRY(hipMemsetAsync(d->dbg.p, 0xff, (size_t)n_pairs * 16 * sizeof(int32_t), st));
-        a.dbg = (int32_t *)d->dbg.p;
-    }
-    { const int ms = p->P - 1; for (int l = 0; l < ms; ++l) for (int m = 0; m < ms; ++m) a.M[ms * l + m] = p->matrix[ms * l + m]; }
-
-    // the pairs that do not run: path length 0, errorType 0, no cells
-    FILL_TRY(queue_fill(d, st, d_alnlen, (size_t)n_pairs * sizeof(int32_t), 0));
-    FILL_TRY(queue_fill(d, st, d_err, (size_t)n_pairs * sizeof(int16_t), 0));
-    FILL_TRY(queue_fill(d, st, d->cells.p, (size_t)n_pairs * sizeof(unsigned long long), 0));
-
-    int grid = 0, window = 0;
-    bool protSmall = false;       // protein, first stage on the 512-row kernel
-    int statMode = -1, statSpec = 0;
-    bool ranMt = false, leanMid = false, startedWide = false, thr768 = false, thr512 = false;
-    bool usedCorridor = false;            // protein: the scores of this call were precomputed in a corridor only
-    bool smallTiles = false;              // the tile jobs of a tile-parallel launch of this call ran on the 512-row window
-    bool probed = false;                  // the level's own sample kept the level off the 512-row window (and set the memory of it)
-    int from512Pairs = -1;                // pairs of a 512-row throughput launch that outgrew it (-1: no such launch)
-    const int32_t *items = (const int32_t *)d->items.p;
-    auto launch_wide = [&](const int32_t *it, int n_it, int *g, int *w) {
-        return prot ? launch_dp<22, 8, 9, false, false, false>(d, st, a, it, n_it, 1, g, w)
-                    : launch_dp<6, 8, 9, false, false, true>(d, st, a, it, n_it, 1, g, w);
-    };
-    if (n_run == 0) rc = TWL_OK;      // nothing to align in this call
-    else if (g_force_global) {
-        rc = prot ? launch_global<22>(d, st, a, items, n_run, seq_len, &grid, &window) : launch_global<6>(d, st, a, items, n_run, seq_len, &grid, &window);
-        snprintf(d->kname, sizeof d->kname, "talco_global_kernel<%d>", prot ? 22 : 6);
-    }
-    else if (prot) {
-        // default: sparse score loop over the non-zero letters of the reference column (matrix mode 3, bit-identical to the dense loop)
-        // TWL_KNOB_PROT_MODE: auto | dense | sparse | presim | r1 (round-1 kernels) | lean_sparse | lean_presim
-        static const char *const kProtModes[] = {"auto", "dense", "sparse", "presim", "r1", "lean_sparse", "lean_presim"};
-        const std::string pcs = kProtModes[std::max(0, std::min(6, g_prot_mode))];
-        // fast_div's guard (talco_nuc.hip.h): non-zero scores within [2^-10, 2^10]
-        bool divOk = true;
-        auto inRange = [](float x) { const float ax = std::fabs(x); return x == 0.0f || (ax >= 0.0009765625f && ax <= 1024.0f); };
-        for (int t = 0; t < 441; ++t) divOk = divOk && inRange(a.M[t]);
-        divOk = divOk && inRange(p->gap_char);
-        const bool lean = divOk && (pcs == "auto" || pcs == "lean_sparse" || pcs == "lean_presim");
-        if (pcs == "r1") rc = launch_dp<22, 8, 1, false, true, true>(d, st, a, items, n_run, 0, &grid, &window);
-        else if (pcs == "dense") rc = launch_dp<22, 8, 2, false, true, true>(d, st, a, items, n_run, 0, &grid, &window);
-        else {
-            // Few pairs (upper tree levels): the serial diagonal chain of each pair is what costs, and most of its instructions are the
-            // column score.  Scores do not depend on the DP state, so the otherwise idle CUs compute them for the whole R x Q matrix
-            // first (score_matrix_kernel, same arithmetic) and the DP kernel only loads them (matrix mode 4).
-            size_t simFloats = 0;
-            std::vector<long long> off((size_t)n_pairs, 0);
-            std::vector<int32_t> blk((size_t)n_pairs + 1, 0);
-            for (int32_t t = 0; t < n_run; ++t) {
-                const int32_t pr = order[t];
-                const long long R = std::max(0, h_len[2 * pr]), Q = std::max(0, h_len[2 * pr + 1]);
-                off[pr] = (long long)simFloats;
-                const long long pitch = (Q + 63) & ~63ll;
-                const bool live = R > 0 && Q > 0;
-                simFloats += live ? (size_t)((R + Q) * pitch) : 0;
-                blk[t + 1] = blk[t] + (live ? (int32_t)(((R + Q - 1 + 63) / 64) * ((Q + 63) / 64)) : 0);
-            }
-            int32_t maxLenP = 0;
-            for (int32_t t = 0; t < 2 * n_pairs; ++t) maxLenP = std::max(maxLenP, h_len[t]);
-            const bool few = n_run <= std::max(1, d->num_cu / 2);      // measured break-even vs the sparse in-kernel path: ~150 pairs of 2 kaa
-            const bool fits = simFloats * sizeof(float) <= ((size_t)16 << 30) && blk[n_run] > 0;
-            if ((rc = d->m24.ensure(21 * 24 * sizeof(float)))) return rc;
-            std::vector<float> m24(21 * 24, 0.0f);
-            for (int l = 0; l < 21; ++l) for (int m = 0; m < 21; ++m) m24[24 * l + m] = a.M[21 * l + m];
-            HIP_TRY(hipMemcpyAsync(d->m24.p, m24.data(), m24.size() * sizeof(float), hipMemcpyHostToDevice, st));
-            HIP_TRY(hipStreamSynchronize(st));      // m24 goes out of scope
-            // CUs/2 < pairs <= CUs: speculative teams of the 512-row geometry, two workgroups per CU, on precomputed scores (as the nucleotide
-            // path does with its throughput geometry)
-            const bool sharedSpec = lean && pcs == "auto" && !few && n_run <= d->num_cu && maxLenP <= 65535 && fits && !d->dump_on && !g_no_spec;
-            const bool presim = (pcs == "presim" || pcs == "lean_presim" || (pcs == "auto" && few) || sharedSpec) && fits && !d->dump_on;
-            statMode = presim ? 4 : 3;
-            if (presim) {
-                if ((rc = d->sim.ensure(simFloats * sizeof(float)))) return rc;
-                if ((rc = d->sim_off.ensure(off.size() * sizeof(long long)))) return rc;
-                if ((rc = d->blk_off.ensure(blk.size() * sizeof(int32_t)))) return rc;
-                HIP_TRY(hipMemcpyAsync(d->sim_off.p, off.data(), off.size() * sizeof(long long), hipMemcpyHostToDevice, st));
-                HIP_TRY(hipMemcpyAsync(d->blk_off.p, blk.data(), blk.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-                HIP_TRY(hipStreamSynchronize(st));      // the host vectors above go out of scope
-                twl::ScoreArgs sa{};
-                sa.cols = a.cols; sa.len = d_len; sa.num = d_num; sa.items = items; sa.blk_off = (const int32_t *)d->blk_off.p;
-                sa.n_items = n_run; sa.seq_len = seq_len; sa.gap_char = p->gap_char; sa.gc_zero = a.gc_zero; sa.M24 = (const float *)d->m24.p;
-                sa.sim = (float *)d->sim.p; sa.sim_off = (const long long *)d->sim_off.p;
-                // (the lean kernels check what they read; the round-1 kernel behind `dense` does not.  A pair that leaves the corridor is re-run by the kernel that scores
-                //  in line, at a hundred times what the corridor saved on it: the first such pair takes the rest of the pass off the corridor -- bands widen and paths
-                //  wander up the tree -- and a level LARGER than the one before it is another pass or family and starts afresh, as the 512-row window does)
-                if (n_run > d->corridor_last_n) d->corridor_lost = false;
-                d->corridor_last_n = n_run;
-                sa.corridor = (lean && !d->corridor_lost) ? g_prot_corridor : 0;
-                usedCorridor = sa.corridor > 0;
-                FILL_TRY(flush_fills(d, st));
-                hipLaunchKernelGGL(twl::score_matrix_kernel<22>, dim3((unsigned)blk[n_run]), dim3(256), 0, st, sa);
-                HIP_TRY(hipGetLastError());
-                a.sim = (const float *)d->sim.p;
-                a.sim_off = (const long long *)d->sim_off.p;
-                statSpec = sharedSpec ? 2 : ((lean && 2 * n_run <= d->num_cu && maxLenP <= 65535 && !g_no_spec) ? 1 : 0);
-                long long sumLenP = 0;
-                for (int32_t t = 0; t < n_run; ++t) sumLenP += (long long)h_len[2 * order[t]] + h_len[2 * order[t] + 1];
-                // tile-parallel (talco_nuc.hip.h, MT kernels) on the precomputed scores: pairs of 2 kaa have 4-5 tiles each
-                const bool mtOkP = lean && pcs == "auto" && n_run <= g_mt_max_pairs && n_run <= d->num_cu && p->marker >= g_mt_min_marker && sumLenP >= 3ll * p->marker * n_run;
-                if (mtOkP) { rc = launch_mt<22, 4, 1>(d, st, a, items, order, n_run, h_len, &grid, &window); statSpec = 3; ranMt = true; protSmall = false; }
-                else if (sharedSpec) { rc = launch_lean<22, 8, 1, 4, 4, true>(d, st, a, items, n_run, &grid, &window); protSmall = true; }
-                else if (lean && 2 * n_run <= d->num_cu && maxLenP <= 65535 && !g_no_spec) rc = launch_lean<22, 16, 1, 4, 1, true>(d, st, a, items, n_run, &grid, &window);
-                else if (lean) rc = launch_lean<22, 16, 1, 4, 1>(d, st, a, items, n_run, &grid, &window);
-                else rc = launch_dp<22, 8, 2, false, true, true, 1, 4>(d, st, a, items, n_run, 0, &grid, &window);
-            } else if (d->dump_on) {      // twl_dp_column_scores: the sparse in-kernel score loop, every visited cell written out
-                if (!lean || n_run != 1) { g_err = "score dump: one pair, matrix within the fast-division range"; return TWL_ERR_UNSUPPORTED; }
-                rc = launch_lean<22, 16, 1, 3, 1, false, true>(d, st, a, items, n_run, &grid, &window);
-            } else if (lean && n_run > d->num_cu) {
-                // more pairs than CUs: the 512-row window (8 waves, one block each; protein bands of 2 kaa pairs are ~270 rows wide, ~400
-                // at most) keeps the ring at 61 KB, so two workgroups share a CU like in the nucleotide throughput kernel; a pair
-                // whose band outgrows it goes to the 1024-row kernel below
-                rc = launch_lean<22, 8, 1, 3, 4>(d, st, a, items, n_run, &grid, &window);
-                protSmall = true;
-            } else if (lean) {
-                rc = launch_lean<22, 16, 1, 3, 1>(d, st, a, items, n_run, &grid, &window);
-            } else {
-                rc = launch_dp<22, 8, 2, false, true, true, 1, 3>(d, st, a, items, n_run, 0, &grid, &window);
-            }
-        }
-    }
-    else {
-        NucFacts nf;
-        nf.n_run = n_run; nf.num_cu = d->num_cu; nf.marker = p->marker; nf.M = a.M; nf.gap_char = p->gap_char; nf.qry_onehot = qry_onehot; nf.shape = shape; nf.dump = d->dump_on;
-        nf.wide_streak = d->wide_streak; nf.last_wide_pct = d->last_wide_pct; nf.wide_calls = d->wide_calls; nf.small_state = (n_run > d->small_last_n) ? 0 : d->small_state; nf.h_len = h_len; nf.order = order.data();
-        const NucPlan pl = plan_nucleotide(nf, current_knobs());
-        if (pl.first == NucFirst::Throughput && (pl.small || pl.held_back)) { if (n_run > d->small_last_n) d->small_state = 0; d->small_last_n = n_run; }
-        const int mm = pl.mm;
-        const bool mm5 = pl.mm5;
-        statMode = mm5 ? 5 : mm;
-        leanMid = pl.lean && mm == 2;
-        TRACE("plan: %s%s, matrix mode %d%s", nuc_first_name(pl.first), pl.small ? " (512-row window, five workgroups per CU)" : "", mm, mm5 ? " (one-letter query rows)" : "");
-        switch (pl.first) {
-        case NucFirst::Dump:      // twl_dp_column_scores: the same kernel code with the score of every visited cell written out
-            if (!pl.lean || n_run != 1) { g_err = "score dump: one pair, matrix within the fast-division range"; return TWL_ERR_UNSUPPORTED; }
-            if (mm5) rc = launch_lean<6, 16, 1, 5, 1, false, true>(d, st, a, items, n_run, &grid, &window);
-            else if (mm == 2) rc = launch_lean<6, 16, 1, 2, 1, false, true>(d, st, a, items, n_run, &grid, &window);
-            else if (mm == 1) rc = launch_lean<6, 16, 1, 1, 1, false, true>(d, st, a, items, n_run, &grid, &window);
-            else rc = launch_lean<6, 16, 1, 0, 1, false, true>(d, st, a, items, n_run, &grid, &window);
-            break;
-        case NucFirst::WideMt:
-            rc = launch_mt<6, 2, 3, true, 4>(d, st, a, items, order, n_run, h_len, &grid, &window);
-            statSpec = 3; ranMt = true; startedWide = true;
-            break;
-        case NucFirst::Mt:        // few pairs of many tiles each: all tiles of all pairs side by side from predicted starts (talco_nuc.hip.h, MT kernels)
-            smallTiles = nf.small_state > 0;      // (the throughput levels of this pass fitted the 512-row window: so do the tiles of their pairs' descendants, until they do not)
-            rc = launch_mt<6, 2, 3, false, 4>(d, st, a, items, order, n_run, h_len, &grid, &window, smallTiles, pl.sp);
-            statSpec = 3; ranMt = true;
-            break;
-        case NucFirst::SpecShared:
-            rc = launch_lean<6, 8, 2, 2, 4, true>(d, st, a, items, n_run, &grid, &window);
-            statMode = 2; statSpec = 2;
-            break;
-        case NucFirst::Spec16:
-            rc = mm5 ? launch_lean<6, 16, 1, 5, 1, true>(d, st, a, items, n_run, &grid, &window) : launch_lean<6, 16, 1, 2, 1, true>(d, st, a, items, n_run, &grid, &window);
-            statSpec = 1;
-            break;
-        case NucFirst::Few16:
-            if (mm5) rc = launch_lean<6, 16, 1, 5, 1>(d, st, a, items, n_run, &grid, &window);
-            else if (mm == 2) rc = launch_lean<6, 16, 1, 2, 1>(d, st, a, items, n_run, &grid, &window);
-            else if (mm == 1) rc = launch_lean<6, 16, 1, 1, 1>(d, st, a, items, n_run, &grid, &window);
-            else rc = launch_lean<6, 16, 1, 0, 1>(d, st, a, items, n_run, &grid, &window);
-            break;
-        case NucFirst::Throughput: {
-            // Default matrix structure (modes 2 and 5): 4 waves x 3 blocks, a 768-row window, FOUR workgroups per CU (round 4: the same 16 waves per CU as
-            // 8 waves x 2 blocks twice, but four independent anti-diagonal chains per SIMD instead of two, a barrier of four waves instead of eight, and no
-            // first products kept per row -- 2048 pairs of 10 kbp 120 -> 95 ms, a leaf level 96 -> 66 ms, tools/exp_thr.py); a pair whose band outgrows 640
-            // rows re-runs on 8 waves x 2 blocks (1024 rows) below.
-            const int bulk = pl.bulk, tail = pl.tail;
-#if defined(TWL_EXP_THR_W)      // geometry experiments (tools/exp_thr.py on cross-compiled variants): waves, blocks per wave, waves per SIMD of the throughput launch
-            if (mm5) rc = launch_lean<6, TWL_EXP_THR_W, TWL_EXP_THR_RPL, 5, TWL_EXP_THR_MINW>(d, st, a, items, bulk, &grid, &window);
-            else if (mm == 2) rc = launch_lean<6, TWL_EXP_THR_W, TWL_EXP_THR_RPL, 2, TWL_EXP_THR_MINW>(d, st, a, items, bulk, &grid, &window);
-#else
-            bool small = pl.small;
-            int done = 0;                 // pairs of the bulk the sample launch took
-            if (pl.probe && bulk >= 8 * d->num_cu) {
-                // the sample: one pair per CU, every (bulk / CUs)-th of the cost order, moved to the front of the launch order
-                const int S = d->num_cu;
-                std::vector<int32_t> front, rest;
-                front.reserve((size_t)S); rest.reserve((size_t)bulk);
-                for (int t = 0, nextPick = 0, j = 0; t < bulk; ++t) {
-                    if (j < S && t == nextPick) { front.push_back(order[t]); ++j; nextPick = (int)((long long)j * bulk / S); }
-                    else rest.push_back(order[t]);
-                }
-                std::copy(front.begin(), front.end(), order.begin());
-                std::copy(rest.begin(), rest.end(), order.begin() + (std::ptrdiff_t)front.size());
-                HIP_TRY(hipMemcpyAsync(d->items.p, order.data(), (size_t)bulk * sizeof(int32_t), hipMemcpyHostToDevice, st));
-                done = (int)front.size();
-                rc = launch_thr<4, 2, 5>(d, st, a, items, done, &grid, &window, mm5, pl.sp);
-                if (rc) return rc;
-                if ((size_t)n_pairs * sizeof(int16_t) > d->probe_cap) {
-                    if (d->probe_h) (void)hipHostFree(d->probe_h);
-                    d->probe_h = nullptr; d->probe_cap = 0;
-                    HIP_TRY(hipHostMalloc((void **)&d->probe_h, (size_t)n_pairs * sizeof(int16_t) * 2, hipHostMallocDefault));
-                    d->probe_cap = (size_t)n_pairs * sizeof(int16_t) * 2;
-                }
-                HIP_TRY(hipMemcpyAsync(d->probe_h, d_err, (size_t)n_pairs * sizeof(int16_t), hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipStreamSynchronize(st));
-                int outgrew = 0;
-                for (int32_t pr : front) outgrew += ((const int16_t *)d->probe_h)[pr] == twl::kErrOverflow ? 1 : 0;
-                small = outgrew * 100 <= 1 * done;
-                d->small_state = small ? 1 : -1;          // (the levels that follow in this pass do as this one did)
-                probed = !small;                          // (a sample that said yes leaves the verdict to the whole level, below)
-                TRACE("sample of %d pairs on the 512-row window: %d outgrew it -> the level runs on %d rows", done, outgrew, small ? 512 : 768);
-                d->kname[0] = 0;                          // (the level's kernel is the one the rest runs on)
-            }
-            if (small && (mm5 || mm == 2)) rc = launch_thr<4, 2, 5>(d, st, a, items + done, bulk - done, &grid, &window, mm5, pl.sp);
-            else if (mm5 || mm == 2) rc = launch_thr<4, 3, 4>(d, st, a, items + done, bulk - done, &grid, &window, mm5, pl.sp);
-#endif
-            else if (mm == 1) rc = launch_lean<6, 8, 2, 1, 2>(d, st, a, items, bulk, &grid, &window);
-            else rc = launch_lean<6, 8, 2, 0, 2>(d, st, a, items, bulk, &grid, &window);
-#if defined(TWL_EXP_THR_W)
-            const bool small = false;
-#endif
-            thr768 = pl.four && !small;      // (after a sample that said no, its own pairs that outgrew 512 rows go straight on to the 1024-row window with the rest's)
-            thr512 = small;
-            if (!rc && tail > 0) {
-                const std::vector<int32_t> tailOrder(order.begin() + bulk, order.begin() + n_run);
-                int g2 = 0, w2 = 0;
-                // (one-letter query rows: the tiles too take the four-product form of the column score)
-                smallTiles = small && !probed;
-                rc = mm5 ? launch_mt<6, 5, 3, false, 4>(d, st, a, items + bulk, tailOrder, tail, h_len, &g2, &w2, smallTiles, pl.sp)
-                         : launch_mt<6, 2, 3, false, 4>(d, st, a, items + bulk, tailOrder, tail, h_len, &g2, &w2, smallTiles, pl.sp);
-                ranMt = true;
-            }
-            break;
-        }
-        default:                  // scores outside the fast division's range: the round-1 kernels (IEEE division)
-            if (mm == 2) rc = launch_dp<6, 8, 2, false, true, true, 4, 2>(d, st, a, items, n_run, 0, &grid, &window);
-            else if (mm == 1) rc = launch_dp<6, 8, 2, false, true, true, 4, 1>(d, st, a, items, n_run, 0, &grid, &window);
-            else rc = launch_dp<6, 8, 2, false, true, true, 4, 0>(d, st, a, items, n_run, 0, &grid, &window);
-        }
-    }
-    if (rc) return rc;
-    FILL_TRY(flush_fills(d, st));      // (nothing ran: the outputs are still to be zeroed)
-    HIP_TRY(hipEventRecord(d->ev[2], st));
-    d->stats.n_launches = 1;
-    d->stats.grid = grid;
-    d->stats.window = window;
-    d->stats.matrix_mode = statMode;
-    d->stats.speculative = statSpec;
-    memcpy(d->stats.kernel, d->kname, sizeof d->stats.kernel);
-
-    // Pairs whose band outgrew a window are re-run, bit-identically, by the next stage: 1024-row fast window ->
-    // 2048-row window (16 waves x 2 blocks, LDS ring) -> 4608-row window (covers flen = 4096; columns from L2/HBM).
-    // (error codes, band cells and the tile-parallel counters come back in ONE synchronisation when nothing has to be re-run -- the common case)
-    std::vector<int16_t> h_err((size_t)n_pairs);
-    std::vector<unsigned long long> cells((size_t)n_pairs);
-    unsigned long long mtStat[4] = {0, 0, 0, 0};
-    bool redoMt = false;      // a re-run went through the tile-parallel path (launch_mt, WIDE)
-    int widePairs = 0;        // pairs that went on to the wide window
-    // (one small kernel writes them into a pinned host block: three device-to-host copies into pageable memory before)
-    const size_t resBytes = 4 * sizeof(unsigned long long) + (size_t)n_pairs * (sizeof(unsigned long long) + sizeof(int32_t) + sizeof(int16_t));
-    if (resBytes > d->res_cap) {
-        if (d->res_h) (void)hipHostFree(d->res_h);
-        d->res_h = nullptr; d->res_cap = 0;
-        HIP_TRY(hipHostMalloc((void **)&d->res_h, resBytes + resBytes / 2, hipHostMallocDefault));
-        d->res_cap = resBytes + resBytes / 2;
-    }
-    auto collect = [&](bool withCells) -> int {
-        hipLaunchKernelGGL(twl::collect_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, st, (int)n_pairs, (const int16_t *)d_err, (const int32_t *)d_alnlen,
-                           (const unsigned long long *)d->cells.p, (ranMt || redoMt) ? (const unsigned long long *)d->mt_stat.p : nullptr, (unsigned long long *)d->res_h);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(st));
-        const unsigned long long *r = (const unsigned long long *)d->res_h;
-        const int32_t *rl = (const int32_t *)(r + 4 + n_pairs);
-        const int16_t *re = (const int16_t *)(rl + n_pairs);
-        std::copy(re, re + n_pairs, h_err.begin());
-        d->last_alnlen.assign(rl, rl + n_pairs);
-        if (withCells) { std::copy(r + 4, r + 4 + n_pairs, cells.begin()); if (ranMt || redoMt) for (int t = 0; t < 4; ++t) mtStat[t] = r[t]; }
-        return TWL_OK;
-    };
-    bool reran = false;
-    float ms_redo = 0.f;
-    for (int stage = 1; stage <= 2; ++stage) {
-        if ((rc = collect(!reran))) return rc;
-        if (stage == 1) TRACE("dp kernel done");
-        // first the pairs with an operand outside the fast division's range (lean kernels only): the IEEE-division kernel of the same window
-        std::vector<int32_t> redo;
-        for (int32_t n = 0; n < n_pairs; ++n) if (h_err[n] == twl::kErrGuard) redo.push_back(n);
-        const bool guardRound = !redo.empty();
-        if (guardRound && usedCorridor) d->corridor_lost = true;
-        if (guardRound) --stage;      // (the window stages follow once these are done)
-        else for (int32_t n = 0; n < n_pairs; ++n) if (h_err[n] == twl::kErrOverflow) redo.push_back(n);
-        if (redo.empty()) break;
-        const bool mid = (stage == 1) && (!prot || protSmall) && !startedWide;      // (a call that started on the 3072-row geometry goes on to the widest kernel)
-        HIP_TRY(hipMemcpyAsync(d->items.p, redo.data(), redo.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipEventRecord(d->ev[3], st));
-        int grid2 = 0, w2 = 0;
-        const bool from512 = thr512 && !guardRound;      // the 512-row throughput window was outgrown: the 768-row throughput geometry takes these pairs, then the stages below
-        const bool from768 = thr768 && !guardRound && !from512;      // the throughput launch's 768-row window was outgrown: first the 1024-row one (8 waves x 2 blocks), then the stages below
-        if (from512) {
-            thr512 = false; --stage;
-            from512Pairs = (int)redo.size();
-            // a few LONG pairs (8+ tiles each): all their tiles at once (1024-row stitch window) instead of one pair after the other for a pair's full latency
-            long long redoLen = 0;
-            for (int32_t n : redo) redoLen += (long long)h_len[2 * n] + h_len[2 * n + 1];
-            const bool viaMt = (int)redo.size() <= g_mt_max_pairs && p->marker >= g_mt_min_marker && redoLen >= 8ll * p->marker * (long long)redo.size() && !d->dump_on;
-            if (viaMt) {
-                rc = (statMode == 5) ? launch_mt<6, 5, 3, false, 4>(d, st, a, (const int32_t *)d->items.p, redo, (int)redo.size(), h_len, &grid2, &w2)
-                                     : launch_mt<6, 2, 3, false, 4>(d, st, a, (const int32_t *)d->items.p, redo, (int)redo.size(), h_len, &grid2, &w2);
-                redoMt = true;       // (what outgrows that goes on to the 3072-row stage)
-            } else {
-                thr768 = true;
-                rc = (statMode == 5) ? launch_lean<6, 4, 3, 5, 4>(d, st, a, (const int32_t *)d->items.p, (int)redo.size(), &grid2, &w2)
-                                     : launch_lean<6, 4, 3, 2, 4>(d, st, a, (const int32_t *)d->items.p, (int)redo.size(), &grid2, &w2);
-            }
-        }
-        else if (from768) {
-            thr768 = false; --stage;
-            rc = (statMode == 5) ? launch_lean<6, 8, 2, 5, 4>(d, st, a, (const int32_t *)d->items.p, (int)redo.size(), &grid2, &w2)
-                                 : launch_lean<6, 8, 2, 2, 4>(d, st, a, (const int32_t *)d->items.p, (int)redo.size(), &grid2, &w2);
-        }
-        else if (guardRound) rc = prot ? launch_dp<22, 8, 2, false, true, true, 1, 3>(d, st, a, (const int32_t *)d->items.p, (int)redo.size(), 0, &grid2, &w2)
-                                  : launch_dp<6, 16, 2, false, true, true, 1, 0>(d, st, a, (const int32_t *)d->items.p, (int)redo.size(), 0, &grid2, &w2);
-        else if (mid && prot) rc = launch_lean<22, 16, 1, 3, 1>(d, st, a, (const int32_t *)d->items.p, (int)redo.size(), &grid2, &w2);
-        // nucleotide, default matrix structure: every tile of these pairs at once on a 3072-row window (launch_mt, WIDE) when they have tiles
-        // to spread; otherwise the lean kernel on a 2048-row window (8 waves x 4 blocks, reference ring still in LDS), tile after tile
-        else if (mid && leanMid) {
-            long long redoLen = 0;
-            for (int32_t n : redo) redoLen += (long long)h_len[2 * n] + h_len[2 * n + 1];
-            const bool wideMt = g_mt_wide && (int)redo.size() <= g_mt_max_pairs && p->marker >= g_mt_min_marker && redoLen >= 3ll * p->marker * (long long)redo.size();
-            widePairs += (int)redo.size();
-            if (wideMt) { rc = launch_mt<6, 2, 3, true, 4>(d, st, a, (const int32_t *)d->items.p, redo, (int)redo.size(), h_len, &grid2, &w2); redoMt = true; }
-            else rc = launch_lean<6, 8, 4, 2, 2>(d, st, a, (const int32_t *)d->items.p, (int)redo.size(), &grid2, &w2);
-        }
-        else if (mid) rc = launch_dp<6, 16, 2, false, true, true, 1, 0>(d, st, a, (const int32_t *)d->items.p, (int)redo.size(), 0, &grid2, &w2);
-        else rc = launch_wide((const int32_t *)d->items.p, (int)redo.size(), &grid2, &w2);
-        if (rc) return rc;
-        reran = true;
-        HIP_TRY(hipEventRecord(d->ev[4], st));
-        HIP_TRY(hipStreamSynchronize(st));
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, d->ev[3], d->ev[4]));
-        ms_redo += ms;
-        d->stats.n_launches += 1;
-        d->stats.n_relaunched += (int32_t)redo.size();
-        if (!mid && !guardRound && !from768 && !from512) { stage = 2; }
-    }
-    // how the fast window fared (see wideFirst): every pair of a small call outgrew it / the call started wide -> the streak goes on
-    if (!prot && leanMid && n_run > 0 && n_run <= 8) d->wide_streak = (startedWide || (redoMt && d->stats.n_relaunched >= n_run)) ? d->wide_streak + 1 : 0;
-    if (!prot && leanMid && n_run > 0) {
-        if (startedWide) d->wide_calls += 1;
-        else { d->last_wide_pct = (int)(100ll * widePairs / n_run); d->wide_calls = 0; }
-    }
-    // tiles that outgrew the 512-row window were computed in line by the stitch launch, one after the other per pair -- the expensive way to lose (10 000 x 10 kbp:
-    // its levels 6 and 7, where tiles begin to outgrow 512 rows, took 34 and 33 ms instead of 23 and 16 with a 2 % allowance): ANY tile in line takes the pass off it
-    if (smallTiles && g_thr_small == 0 && mtStat[1] > 0ull) d->small_state = -1;
-    // how the 512-row throughput window fared (plan_nucleotide, small): a level that sent more than 1 % of its pairs on (5 % when they are long) keeps the rest
-    // of the pass off it, one that fitted lets the next level start on it
-    if (probed || g_thr_small != 0) {}
-    else if (thr512 || from512Pairs >= 0) {
-        const long long longestRun = n_run > 0 ? (long long)h_len[2 * order[0]] + h_len[2 * order[0] + 1] : 0;      // (order[0] is the longest pair, or one of the sample's: lengths of a level are alike)
-        d->small_state = (std::max(from512Pairs, 0) * 100ll > (longestRun <= 4096 ? 1ll : 5ll) * n_run) ? -1 : 1;   // (long pairs re-run tile-parallel: the bet is lost later)
-    }
-    // a band that outgrew even the widest window (only possible with flen > 4096, i.e. in a retry of the deferred pass)
-    if (reran) {
-        const unsigned long long keep[4] = {mtStat[0], mtStat[1], mtStat[2], mtStat[3]};
-        if ((rc = collect(true))) return rc;
-        for (int t = 0; t < 4; ++t) mtStat[t] = keep[t] + (redoMt ? mtStat[t] : 0ull);      // (the counters of the first launch, plus those of a tile-parallel re-run)
-    }
-    // A band that outgrew even the 4608-row window (only possible with flen > 4608, i.e. in a retry of the deferred pass, alignment-cpu.cpp:116-129), or an
-    // operand outside the fast division's range that met such a band: the global-memory kernel, which has no window and divides the IEEE way (round 5;
-    // TWL_ERR_UNSUPPORTED ended the run here before)
-    {
-        std::vector<int32_t> redo;
-        for (int32_t n = 0; n < n_pairs; ++n) if (h_err[n] == twl::kErrOverflow || h_err[n] == twl::kErrGuard) redo.push_back(n);
-        if (!redo.empty()) {
-            HIP_TRY(hipMemcpyAsync(d->items.p, redo.data(), redo.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-            HIP_TRY(hipEventRecord(d->ev[3], st));
-            int grid2 = 0, w2 = 0;
-            rc = prot ? launch_global<22>(d, st, a, (const int32_t *)d->items.p, (int)redo.size(), seq_len, &grid2, &w2)
-                      : launch_global<6>(d, st, a, (const int32_t *)d->items.p, (int)redo.size(), seq_len, &grid2, &w2);
-            if (rc) return rc;
-            HIP_TRY(hipEventRecord(d->ev[4], st));
-            HIP_TRY(hipStreamSynchronize(st));
-            float ms = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms, d->ev[3], d->ev[4]));
-            ms_redo += ms;
-            d->stats.n_launches += 1;
-            d->stats.n_relaunched += (int32_t)redo.size();
-            d->stats.window = std::max(d->stats.window, w2);
-            const unsigned long long keep[4] = {mtStat[0], mtStat[1], mtStat[2], mtStat[3]};
-            if ((rc = collect(true))) return rc;
-            for (int t = 0; t < 4; ++t) mtStat[t] = keep[t];
-        }
-    }
-    for (int32_t n = 0; n < n_pairs; ++n)
-        if (h_err[n] == twl::kErrOverflow || h_err[n] == twl::kErrGuard) { g_err = "internal: a re-run code survived the global-memory kernel"; return TWL_ERR_HIP; }
-    uint64_t total = 0;
-    for (int32_t n = 0; n < n_pairs; ++n) { d->pair_cells[n] = cells[n]; total += cells[n]; }
-    if (ranMt || redoMt) { d->stats.mt_tiles_predicted = (int32_t)mtStat[0]; d->stats.mt_tiles_inline = (int32_t)mtStat[1]; d->stats.mt_scouts_failed = (int32_t)mtStat[2]; }
-    d->last_err = h_err;      // (twl_level_align hands them to its caller without another copy)
-    // the global-memory kernel's scratch does not stay next to a resident store for the rest of the run (every launch of the call has been waited for)
-    if (d->gtb.cap > ((size_t)256 << 20)) d->gtb.release();
-    if (want_dbg) {
-        d->dbg_host.resize((size_t)n_pairs * 16);
-        HIP_TRY(hipMemcpy(d->dbg_host.data(), d->dbg.p, d->dbg_host.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-        for (int32_t n = 0; n < n_pairs && n < 64; ++n) {
-            const int32_t *g = &d->dbg_host[(size_t)n * 16];
-            fprintf(stderr, "[twl dbg] pair %d: tiles %d last_k %d conv 0x%x L %d U %d ref_idx %d qry_idx %d pos %d err %d steps_left %d R %d Q %d\n",
-                    n, g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8], g[9], g[10], g[11]);
-        }
-    }
-    // work done by the abandoned fast-window attempts is real GPU work but not algorithmic cells: not counted
-    float ms_pack = 0.f, ms_k = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms_pack, d->ev[0], d->ev[1]));
-    HIP_TRY(hipEventElapsedTime(&ms_k, d->ev[1], d->ev[2]));
-    d->stats.band_cells = total;
-    d->stats.nominal_cells = nominal;
-    d->stats.pack_ms = ms_pack;
-    d->stats.kernel_ms = ms_k + ms_redo;
-    d->stats.total_ms = ms_pack + ms_k + ms_redo;
-    return TWL_OK;
-}
+#include "twl_run.inc.hip"
 
 }  // namespace
 
@@ -1088,33 +582,37 @@ int twl_set_knob(int key, int value)
     case TWL_KNOB_POISON_TB: g_poison_tb = value ? 1 : 0; return TWL_OK;
     case TWL_KNOB_MT_ANCHOR: g_mt_anchor = value ? 1 : 0; return TWL_OK;
     case TWL_KNOB_MT_LEAD2: if (value < 0) { g_mt_lead2 = 96; g_mt_lead2_lat = 128; } else g_mt_lead2 = g_mt_lead2_lat = std::max(16, value); return TWL_OK;
-    case TWL_KNOB_PROT_CORRIDOR: g_prot_corridor = std::max(0, value); for (auto *d : g_devs) { d->corridor_lost = false; d->corridor_last_n = 0; } return TWL_OK;      // (and forgets what earlier levels found)
+    case TWL_KNOB_PROT_CORRIDOR: g_prot_corridor = std::max(0, value); for (auto *d : g_devs) d->mem.forget_corridor(); return TWL_OK;      // (and forgets what earlier levels found)
     case TWL_KNOB_SCOUT_XDROP_PCT: g_scout_xdrop_pct = std::max(10, std::min(100, value)); return TWL_OK;
-    case TWL_KNOB_THR_SMALL: g_thr_small = std::max(0, std::min(2, value)); for (auto *d : g_devs) d->small_state = d->small_last_n = 0; return TWL_OK;      // (and forgets what earlier levels found)
+    case TWL_KNOB_THR_SMALL: g_thr_small = std::max(0, std::min(2, value)); for (auto *d : g_devs) d->mem.forget_small(); return TWL_OK;      // (and forgets what earlier levels found)
     default: g_err = "unknown knob"; return TWL_ERR_BAD_ARGUMENT;
     }
 }
 
 #include "twl_comm.inc.hip"
 
-// The launch plan of a nucleotide call, as run_device would make it, in words: no device is touched (unit tests of the policy on a CPU-only box).
+// The launch plan of a call, as run_device would make it, in words: no device is touched (unit tests of the policy on a CPU-only box).
 int twl_plan_describe(const twl_params *p, int32_t n_pairs, const int32_t *len, int32_t num_cu, int32_t qry_onehot, int32_t wide_streak, char *out, int32_t cap)
 {
-    // (wide_streak >= 1000 encodes the other memory of the device: 1000 + 10 * calls started wide + (1 if three quarters of the last narrow-first call went wide);
-    //  + 100000 * (32 + what the pass remembers of the 512-row throughput window, NucFacts::small_state: -1 / 1) when that is not 0)
-    const int small_state = wide_streak >= 100000 ? wide_streak / 100000 - 32 : 0;
-    wide_streak %= 100000;
-    if (!p || p->P != 6 || n_pairs < 0 || (n_pairs > 0 && !len) || num_cu < 1 || !out || cap < 64) { g_err = "bad argument (nucleotide parameters, a buffer of 64+ bytes)"; return TWL_ERR_BAD_ARGUMENT; }
+    if (!p || (p->P != 6 && p->P != 22) || n_pairs < 0 || (n_pairs > 0 && !len) || num_cu < 1 || !out || cap < 64) { g_err = "bad argument (nucleotide or protein parameters, a buffer of 64+ bytes)"; return TWL_ERR_BAD_ARGUMENT; }
+    const PassMemory mem = memory_from_code(wide_streak);
     std::vector<int32_t> order;
     for (int32_t n = 0; n < n_pairs; ++n) if (len[2 * n] > 0 && len[2 * n + 1] > 0) order.push_back(n);
     std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return (int64_t)len[2 * x] + len[2 * x + 1] > (int64_t)len[2 * y] + len[2 * y + 1]; });
-    float M[25];
-    for (int t = 0; t < 25; ++t) M[t] = p->matrix[t];
+    const int ms = p->P - 1;
+    std::vector<float> M(p->matrix, p->matrix + ms * ms);
+    if (p->P == 22) {
+        ProtFacts pf;
+        pf.n_run = (int)order.size(); pf.n_pairs = n_pairs; pf.num_cu = num_cu; pf.marker = p->marker; pf.M = M.data(); pf.gap_char = p->gap_char;
+        pf.corridor_lost = mem.corridor_lost; pf.h_len = len; pf.order = order.data();
+        const ProtPlan pl = plan_protein(pf, current_knobs());
+        const int w = snprintf(out, (size_t)cap, "%s; mode %d; window %d", prot_first_name(pl.first), pl.mm, prot_first_window(pl.first));
+        if (pl.presim && w > 0 && w < cap) snprintf(out + w, (size_t)(cap - w), "; %zu scores precomputed, corridor %d", pl.simFloats, pl.corridor);
+        return TWL_OK;
+    }
     NucFacts nf;
-    nf.n_run = (int)order.size(); nf.num_cu = num_cu; nf.marker = p->marker; nf.M = M; nf.gap_char = p->gap_char; nf.qry_onehot = qry_onehot != 0; nf.wide_streak = wide_streak < 1000 ? wide_streak : 0;
-    if (wide_streak >= 1000) { nf.last_wide_pct = ((wide_streak - 1000) % 10) ? 100 : 0; nf.wide_calls = (wide_streak - 1000) / 10; }
-    nf.small_state = small_state;
-    nf.h_len = len; nf.order = order.data();
+    nf.n_run = (int)order.size(); nf.num_cu = num_cu; nf.marker = p->marker; nf.M = M.data(); nf.gap_char = p->gap_char; nf.qry_onehot = qry_onehot != 0;
+    nf.remember(mem); nf.h_len = len; nf.order = order.data();
     const NucPlan pl = plan_nucleotide(nf, current_knobs());
     snprintf(out, (size_t)cap, "%s; mode %d; window %d%s; bulk %d tail %d", nuc_first_name(pl.first), pl.mm5 ? 5 : pl.mm,
              pl.first == NucFirst::WideMt ? 3072 : ((pl.first == NucFirst::Throughput && pl.small) ? 512 : ((pl.first == NucFirst::Throughput && pl.four) ? 768 : 1024)), pl.probe ? " or 768 (a sample of the level decides)" : "", pl.bulk, pl.tail);

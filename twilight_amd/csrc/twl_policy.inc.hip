@@ -1,16 +1,96 @@
-// twilight_amd/csrc/twl_policy.inc.hip -- the launch policy of a nucleotide call as a PURE function of the call's facts (plan_nucleotide; twl_plan_describe prints it without a device, tests/test_policy_cpu.py holds its cases).
-// Included by twl_align.hip (one translation unit: it shares that file's Device bookkeeping, error string and fill queue).
+// twilight_amd/csrc/twl_policy.inc.hip -- the launch policy of a DP call as PURE functions of the call's facts: the first launch (plan_nucleotide, plan_protein), the rung a set of
+// outgrown pairs takes next (next_rung) and what a device remembers of a pass (PassMemory).  No HIP call in this file: twl_plan_describe prints the plans without a device
+// (tests/test_policy_cpu.py), tests/policy_kats.cpp includes the file directly for the ladder and the memory.  Included by twl_align.hip (one translation unit).
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstdint>
 
-// ---- launch policy of the nucleotide path: a pure function of the call's facts (unit-tested without a GPU through twl_plan_describe) ----
-struct Knobs { int mt_max_pairs, mt_min_marker, mt_tail_pct, mt_wide, assume_onehot_query, no_spec, thr_small; };
+// TWL_KNOB_PROT_MODE: auto | dense | sparse | presim | r1 (round-1 kernels) | lean_sparse | lean_presim
+enum class ProtMode { Auto, Dense, Sparse, Presim, R1, LeanSparse, LeanPresim };
+struct Knobs { int mt_max_pairs, mt_min_marker, mt_tail_pct, mt_wide, assume_onehot_query, no_spec, thr_small; ProtMode prot_mode; int prot_corridor; };
+// fast_div's guard (talco_nuc.hip.h): non-zero scores within [2^-10, 2^10]; anything else takes the IEEE-division kernel
+inline bool fast_div_in_range(const float *M, int n, float gap_char)
+{
+    auto inRange = [](float x) { const float ax = std::fabs(x); return x == 0.0f || (ax >= 0.0009765625f && ax <= 1024.0f); };
+    bool ok = inRange(gap_char);
+    for (int t = 0; t < n; ++t) ok = ok && inRange(M[t]);
+    return ok;
+}
+
+// ---- what ran first (the steps of run_device share it), and what a device remembers of a pass ----
+enum class Level { From512, From768, Mid, Wide, Global };      // where the re-run ladder stands: the window class of what ran last
+struct Ran {
+    bool prot = false;
+    Level start = Level::Wide;            // window class of the first launch: 512- / 768-row throughput, a 1024-row geometry (protein: 512) with the middle rungs ahead, or straight on to the widest kernel
+    int mode = -1, spec = 0;              // twl_stats: matrix_mode (5: one-letter query rows), speculative (1 teams of 16 waves, 2 shared teams, 3 tile-parallel)
+    bool leanMid = false;                 // nucleotide, round-2 kernels, default matrix structure: the middle rung is tile-parallel 3072 / lean 2048
+    bool startedWide = false;             // the first launch was the 3072-row tile-parallel geometry
+    bool ranMt = false;                   // a tile-parallel launch was part of the first launch (its counters are collected)
+    bool smallTiles = false;              // the tile jobs of a tile-parallel launch of this call ran on the 512-row window
+    bool probed = false;                  // the level's own sample kept the level off the 512-row window (and set the memory of it)
+    bool usedCorridor = false;            // protein: the scores of this call were precomputed in a corridor only
+};
+struct LadderOutcome {
+    int relaunched = 0, widePairs = 0;    // pairs re-run by the ladder (all rungs); pairs that went on to the wide window (middle rung)
+    int from512Pairs = -1;                // pairs of a 512-row throughput launch that outgrew it (-1: no such launch)
+    bool redoMt = false, guardRound = false;      // a re-run went through the tile-parallel path; a guard round was needed
+    unsigned long long firstInline = 0;   // tiles the FIRST launch's stitch kernel computed in line (mt_stat[1])
+};
+struct PassMemory {
+    int wide_streak = 0;                            // consecutive small calls whose pairs all outgrew the fast window (plan_nucleotide: wideFirst)
+    int last_wide_pct = 0, wide_calls = 0;          // share of the last narrow-first call's pairs that went on to the wide window; calls started wide since
+    int small_state = 0, small_last_n = 0;          // what the levels of short pairs of this pass found of the 512-row throughput window (1 fits, -1 outgrown), and the pairs of the last such level
+    bool corridor_lost = false; int corridor_last_n = 0;      // protein: a pair of an earlier level of this pass left the corridor of the precomputed scores (the later levels score the whole matrix)
+    void forget_small() { small_state = small_last_n = 0; }
+    void forget_corridor() { corridor_lost = false; corridor_last_n = 0; }
+    // a level LARGER than the one before it is another pass or family and starts afresh: nothing is known again
+    int small_for(int n_run) const { return n_run > small_last_n ? 0 : small_state; }
+    void begin_small_level(int n_run) { small_state = small_for(n_run); small_last_n = n_run; }
+    bool corridor_lost_for(int n_run) const { return n_run > corridor_last_n ? false : corridor_lost; }
+    void begin_corridor_level(int n_run) { corridor_lost = corridor_lost_for(n_run); corridor_last_n = n_run; }
+    void update(const Ran &ran, const LadderOutcome &o, int n_run, long long longestRun, const Knobs &k)
+    {
+        // (the lean kernels check what they read.  A pair that leaves the corridor is re-run by the kernel that scores in line, at a hundred times what the corridor saved
+        //  on it: the first such pair takes the rest of the pass off the corridor -- bands widen and paths wander up the tree)
+        if (o.guardRound && ran.usedCorridor) corridor_lost = true;
+        const bool nucMid = !ran.prot && ran.leanMid && n_run > 0;
+        // how the fast window fared (see wideFirst): every pair of a small call outgrew it / the call started wide -> the streak goes on
+        if (nucMid && n_run <= 8) wide_streak = (ran.startedWide || (o.redoMt && o.relaunched >= n_run)) ? wide_streak + 1 : 0;
+        if (nucMid && ran.startedWide) wide_calls += 1;
+        else if (nucMid) { last_wide_pct = (int)(100ll * o.widePairs / n_run); wide_calls = 0; }
+        // tiles that outgrew the 512-row window were computed in line by the stitch launch, one after the other per pair -- the expensive way to lose (10 000 x 10 kbp:
+        // its levels 6 and 7, where tiles begin to outgrow 512 rows, took 34 and 33 ms instead of 23 and 16 with a 2 % allowance): ANY tile in line takes the pass off it
+        if (ran.smallTiles && k.thr_small == 0 && o.firstInline > 0ull) small_state = -1;
+        // how the 512-row throughput window fared (plan_nucleotide, small): a level that sent more than 1 % of its pairs on (5 % when they are long) keeps the rest
+        // of the pass off it, one that fitted lets the next level start on it.  (longestRun: the longest pair, or one of the sample's: lengths of a level are alike;
+        // long pairs re-run tile-parallel: the bet is lost later.)  A level whose own sample said no has set the memory already.
+        if (!ran.probed && k.thr_small == 0 && ran.start == Level::From512)
+            small_state = (std::max(o.from512Pairs, 0) * 100ll > (longestRun <= 4096 ? 1ll : 5ll) * n_run) ? -1 : 1;
+    }
+};
+// twl_plan_describe's `wide_streak` argument carries the whole memory: below 1000 the streak itself; 1000 + 10 * calls started wide + (1 if three quarters of the last
+// narrow-first call went wide); + 100000 * (32 + small_state: -1 / 1) when the pass remembers something of the 512-row throughput window
+inline PassMemory memory_from_code(int code)
+{
+    PassMemory m;
+    if (code >= 100000) { m.small_state = code / 100000 - 32; m.small_last_n = INT_MAX; }
+    code %= 100000;
+    if (code < 1000) m.wide_streak = code;
+    else { m.last_wide_pct = ((code - 1000) % 10) ? 100 : 0; m.wide_calls = (code - 1000) / 10; }
+    return m;
+}
+
+// ---- launch policy of the nucleotide path ----
 struct NucFacts {
     int n_run = 0, num_cu = 0, marker = 0;
     const float *M = nullptr;             // 5 x 5 matrix
     float gap_char = 0;
     bool qry_onehot = false, dump = false;
     int shape = 0;                        // what the caller knows about every pair: 0 nothing, 2 leaf x leaf (single sequences on both sides)
-    int wide_streak = 0, last_wide_pct = 0, wide_calls = 0;
-    int small_state = 0;                  // the 512-row throughput window (NucPlan::small) on the earlier levels of this pass: 1 they fitted it, -1 one outgrew it, 0 nothing known
+    int wide_streak = 0, last_wide_pct = 0, wide_calls = 0;      // copies of PassMemory's
+    int small_state = 0;                  // PassMemory::small_for(n_run): the 512-row throughput window (NucPlan::small) on the earlier levels of this pass: 1 they fitted it, -1 one outgrew it, 0 nothing known
+    void remember(const PassMemory &m) { wide_streak = m.wide_streak; last_wide_pct = m.last_wide_pct; wide_calls = m.wide_calls; small_state = m.small_for(n_run); }
     const int32_t *h_len = nullptr;       // [pair][2]
     const int32_t *order = nullptr;       // the pairs that run, longest first
 };
@@ -37,11 +117,7 @@ NucPlan plan_nucleotide(const NucFacts &f, const Knobs &k)
     for (int l = 0; l < 4; ++l)
         for (int m = 0; m < 4; ++m) st3 = st3 && M[5 * l + m] == ((l == m) ? M[0] : (((l ^ m) == 2) ? M[2] : M[1]));
     pl.mm = nz ? (st3 ? 2 : 1) : 0;
-    // fast_div's guard (talco_nuc.hip.h): non-zero scores within [2^-10, 2^10]; anything else takes the IEEE-division kernel
-    bool divOk = true;
-    auto inRange = [](float x) { const float ax = std::fabs(x); return x == 0.0f || (ax >= 0.0009765625f && ax <= 1024.0f); };
-    for (int t = 0; t < 25; ++t) divOk = divOk && inRange(M[t]);
-    pl.lean = divOk && inRange(f.gap_char);
+    pl.lean = fast_div_in_range(M, 25, f.gap_char);
     const int mm = pl.mm, n_run = f.n_run;
     // few pairs: one 64-row block per wave (16 waves) for the shortest diagonal step
     const bool few = n_run <= f.num_cu;
@@ -126,4 +202,122 @@ const char *nuc_first_name(NucFirst f)
     }
 }
 
-Knobs current_knobs() { return Knobs{g_mt_max_pairs, g_mt_min_marker, g_mt_tail_pct, g_mt_wide, g_assume_onehot_query, g_no_spec, g_thr_small}; }
+
+// ---- launch policy of the protein path ----
+struct ProtFacts {
+    int n_run = 0, n_pairs = 0, num_cu = 0, marker = 0;
+    const float *M = nullptr;             // 21 x 21 matrix
+    float gap_char = 0;
+    bool dump = false;
+    bool corridor_lost = false;           // PassMemory::corridor_lost_for(n_run)
+    const int32_t *h_len = nullptr;       // [pair][2], all n_pairs of the call
+    const int32_t *order = nullptr;       // the pairs that run, longest first
+};
+enum class ProtFirst { R1, Dense, MtPresim, SpecShared, Spec16, Plain16, Thr512, Sparse16, Ieee, Dump };
+struct ProtPlan {
+    ProtFirst first = ProtFirst::Ieee;
+    int mm = -1;                          // matrix mode 3 sparse score loop in the kernel / 4 precomputed scores (-1: the round-1 kernels behind r1 / dense)
+    bool lean = false;                    // the round-2 kernels (scores within fast_div's range)
+    bool presim = false;                  // score_matrix_kernel runs first ...
+    size_t simFloats = 0;                 // ... into this many floats ...
+    int corridor = 0;                     // ... within this half-width of the diagonal (0: the whole R x Q matrix)
+    int spec = 0;                         // twl_stats.speculative
+    bool small = false;                   // a 512-row geometry: what outgrows it has the 16-wave kernel ahead
+};
+ProtPlan plan_protein(const ProtFacts &f, const Knobs &k)
+{
+    ProtPlan pl;
+    const ProtMode pm = k.prot_mode;
+    const int n_run = f.n_run;
+    // default: sparse score loop over the non-zero letters of the reference column (matrix mode 3, bit-identical to the dense loop)
+    pl.lean = fast_div_in_range(f.M, 441, f.gap_char) && (pm == ProtMode::Auto || pm == ProtMode::LeanSparse || pm == ProtMode::LeanPresim);
+    if (pm == ProtMode::R1 || pm == ProtMode::Dense) { pl.first = pm == ProtMode::R1 ? ProtFirst::R1 : ProtFirst::Dense; return pl; }
+    // Few pairs (upper tree levels): the serial diagonal chain of each pair is what costs, and most of its instructions are the
+    // column score.  Scores do not depend on the DP state, so the otherwise idle CUs compute them for the whole R x Q matrix
+    // first (score_matrix_kernel, same arithmetic) and the DP kernel only loads them (matrix mode 4).
+    int32_t blocks = 0, maxLen = 0;
+    long long sumLen = 0;
+    for (int32_t t = 0; t < n_run; ++t) {
+        const long long R = f.h_len[2 * f.order[t]], Q = f.h_len[2 * f.order[t] + 1];
+        pl.simFloats += (size_t)((R + Q) * ((Q + 63) & ~63ll));
+        blocks += (int32_t)(((R + Q - 1 + 63) / 64) * ((Q + 63) / 64));
+        sumLen += R + Q;
+    }
+    for (int32_t t = 0; t < 2 * f.n_pairs; ++t) maxLen = std::max(maxLen, f.h_len[t]);
+    const bool few = n_run <= std::max(1, f.num_cu / 2);      // measured break-even vs the sparse in-kernel path: ~150 pairs of 2 kaa
+    const bool fits = pl.simFloats * sizeof(float) <= ((size_t)16 << 30) && blocks > 0;
+    // very few pairs: two workgroups per pair take the tiles in turn (the mailbox words of that start carry absolute positions in 16 bits each)
+    const bool spec16 = pl.lean && 2 * n_run <= f.num_cu && maxLen <= 65535 && !k.no_spec;
+    // CUs/2 < pairs <= CUs: speculative teams of the 512-row geometry, two workgroups per CU, on precomputed scores (as the nucleotide
+    // path does with its throughput geometry)
+    const bool sharedSpec = pl.lean && pm == ProtMode::Auto && !few && n_run <= f.num_cu && maxLen <= 65535 && fits && !f.dump && !k.no_spec;
+    pl.presim = (pm == ProtMode::Presim || pm == ProtMode::LeanPresim || (pm == ProtMode::Auto && few) || sharedSpec) && fits && !f.dump;
+    pl.mm = pl.presim ? 4 : 3;
+    // tile-parallel (talco_nuc.hip.h, MT kernels) on the precomputed scores: pairs of 2 kaa have 4-5 tiles each
+    const bool mtOk = pl.lean && pm == ProtMode::Auto && n_run <= k.mt_max_pairs && n_run <= f.num_cu && f.marker >= k.mt_min_marker && sumLen >= 3ll * f.marker * n_run;
+    if (pl.presim) {
+        // (the round-1 kernel behind a matrix outside the range does not check what it reads: the corridor is for the lean kernels; a pass that lost it scores the whole matrix)
+        pl.corridor = (pl.lean && !f.corridor_lost) ? k.prot_corridor : 0;
+        pl.first = mtOk ? ProtFirst::MtPresim : sharedSpec ? ProtFirst::SpecShared : spec16 ? ProtFirst::Spec16 : pl.lean ? ProtFirst::Plain16 : ProtFirst::Ieee;
+    }
+    else if (f.dump) pl.first = ProtFirst::Dump;      // twl_dp_column_scores (one pair, lean: the launch step refuses anything else)
+    // more pairs than CUs: the 512-row window (8 waves, one block each; protein bands of 2 kaa pairs are ~270 rows wide, ~400
+    // at most) keeps the ring at 61 KB, so two workgroups share a CU like in the nucleotide throughput kernel; a pair
+    // whose band outgrows it goes to the 16-wave kernel (1024 rows) by the ladder
+    else if (pl.lean && n_run > f.num_cu) pl.first = ProtFirst::Thr512;
+    else pl.first = pl.lean ? ProtFirst::Sparse16 : ProtFirst::Ieee;
+    pl.spec = pl.first == ProtFirst::MtPresim ? 3 : pl.first == ProtFirst::SpecShared ? 2 : pl.first == ProtFirst::Spec16 ? 1 : 0;
+    pl.small = pl.first == ProtFirst::SpecShared || pl.first == ProtFirst::Thr512;
+    return pl;
+}
+const char *prot_first_name(ProtFirst f)
+{
+    switch (f) {
+    case ProtFirst::R1: return "round-1 kernel, 8 waves x 1 block";
+    case ProtFirst::Dense: return "dense, 8 waves x 2 blocks";
+    case ProtFirst::MtPresim: return "tile-parallel on precomputed scores";
+    case ProtFirst::SpecShared: return "speculative teams, 8 waves x 1 block";
+    case ProtFirst::Spec16: return "speculative teams, 16 waves";
+    case ProtFirst::Plain16: return "16 waves x 1 block on precomputed scores";
+    case ProtFirst::Thr512: return "throughput, 8 waves x 1 block";
+    case ProtFirst::Sparse16: return "16 waves x 1 block";
+    case ProtFirst::Dump: return "dump";
+    default: return "general (IEEE division)";
+    }
+}
+inline int prot_first_window(ProtFirst f) { return (f == ProtFirst::R1 || f == ProtFirst::SpecShared || f == ProtFirst::Thr512) ? 512 : 1024; }
+
+// ---- the re-run ladder: which rung a set of outgrown pairs takes, and where the next round stands ----
+enum class Rung { Guard, Thr768, MtStitch1024, Lean1024, Prot16, Mt3072, Lean2048, Ieee16x2, Wide4608, Global };
+enum class RedoKind { Guard, Overflow };      // pairs with an operand outside the fast division's range / pairs whose band outgrew the window
+struct RedoFacts { int count = 0; long long sumLen = 0; int marker = 0; bool dump = false; };      // the pairs to re-run: how many, their summed R + Q
+struct Step { Rung rung; Level next; };
+Step next_rung(const Ran &ran, Level at, RedoKind kind, const RedoFacts &f, const Knobs &k)
+{
+    if (at == Level::Global) return {Rung::Global, Level::Global};      // no window, IEEE division: takes whatever is left, of either kind
+    // the IEEE-division kernel of the same window; the window rungs follow once these are done
+    if (kind == RedoKind::Guard) return {Rung::Guard, at};
+    const bool tiles = f.count <= k.mt_max_pairs && f.marker >= k.mt_min_marker;
+    switch (at) {
+    case Level::From512:
+        // the 512-row throughput window was outgrown: the 768-row throughput geometry takes these pairs -- unless they are a few LONG pairs (8+ tiles each): then all
+        // their tiles at once (1024-row stitch window) instead of one pair after the other for a pair's full latency
+        if (tiles && f.sumLen >= 8ll * f.marker * (long long)f.count && !f.dump) return {Rung::MtStitch1024, Level::Mid};
+        return {Rung::Thr768, Level::From768};
+    case Level::From768:      // the throughput launch's 768-row window was outgrown: first the 1024-row one (8 waves x 2 blocks)
+        return {Rung::Lean1024, Level::Mid};
+    case Level::Mid:
+        if (ran.prot) return {Rung::Prot16, Level::Wide};
+        if (!ran.leanMid) return {Rung::Ieee16x2, Level::Wide};
+        // nucleotide, default matrix structure: every tile of these pairs at once on a 3072-row window (launch_mt, WIDE) when they have tiles
+        // to spread; otherwise the lean kernel on a 2048-row window (8 waves x 4 blocks, reference ring still in LDS), tile after tile
+        return {(k.mt_wide && tiles && f.sumLen >= 3ll * f.marker * (long long)f.count) ? Rung::Mt3072 : Rung::Lean2048, Level::Wide};
+    default:                  // 4608-row window (8 waves x 9 blocks; covers flen = 4096; columns from L2/HBM)
+        return {Rung::Wide4608, Level::Global};
+    }
+}
+const char *rung_name(Rung r)
+{
+    static const char *const names[] = {"guard (IEEE division)", "throughput 768", "tile-parallel 1024", "lean 1024", "protein 16-wave", "tile-parallel 3072", "lean 2048", "16 x 2 IEEE", "wide 4608", "global"};
+    return names[(int)r];
+}

@@ -2,6 +2,7 @@
 // (/root/reference/src/alignment-helper.cpp, scoring-matrix.cpp, tree.cpp, progressive.cpp).  Prints "OK <name>" / "FAIL <name>".
 #include "../twilight_amd/csrc/host/twl_host.hpp"
 
+#include <algorithm>
 #include <random>
 #include <functional>
 #include <unordered_map>
@@ -341,6 +342,108 @@ int main(int argc, char **argv)
         CHECK("ownership_plan_none_for_too_many_ranks", none.cut == -1 && none.owner.empty());
         CHECK("ownership_plan_none_for_one_rank", progressive::planOwnership(sub, levels, 1).cut == -1);
         delete sub;
+    }
+    // ---- the level policy (level_policy.hpp), from the reference src/alignment-cpu.cpp:88-144 ----
+    {
+        using namespace progressive;
+        // :88  gapCharScore 0 when currentTask is 1 or 2, or a side has more than 10000 sequences
+        bool ok = true;
+        for (int task : {0, 1, 2})
+            for (int r : {1, 10000, 10001})
+                for (int q : {1, 10000, 10001}) {
+                    PairShape s; s.refNum = r; s.qryNum = q; s.refLen = s.qryLen = 10;
+                    ok = ok && zeroGapChar(task, s) == (task == 1 || task == 2 || r == 10001 || q == 10001);
+                }
+        CHECK("policy_zero_gap_char", ok);
+        // :91-92  never in MERGE_MSA; never for a side of several sequences; else the flag of the single sequence
+        CHECK("policy_low_quality_side", !lowQualitySide(true, 1, true) && !lowQualitySide(true, 5, true) && !lowQualitySide(false, 2, true) &&
+                                             lowQualitySide(false, 1, true) && !lowQualitySide(false, 1, false) && !lowQualitySide(false, 7, false));
+        // :89-90,93,95  an empty side gives the all-gap path and no DP; otherwise the DP runs unless a side is low-quality
+        ok = true;
+        const struct { int r, q; const char *path; } shapes[] = {{0, 5, "11111"}, {7, 0, "2222222"}, {0, 0, ""}, {7, 5, ""}};
+        for (auto &c : shapes)
+            for (int flags = 0; flags < 4; ++flags) {
+                PairShape s; s.refLen = c.r; s.qryLen = c.q; s.refNum = s.qryNum = 1; s.lowQ_r = flags & 1; s.lowQ_q = flags & 2;
+                ok = ok && pathStr(trivialPath(s)) == c.path && goesToDp(s) == (c.path[0] == 0 && flags == 0);
+            }
+        CHECK("policy_trivial_path_and_goes_to_dp", ok);
+        // :136-144  task 0 only, a single-sequence side, and a low-quality flag on either side
+        ok = true;
+        const int counts[3][2] = {{1, 5}, {5, 1}, {5, 5}};
+        for (int task : {0, 1})
+            for (int c = 0; c < 3; ++c)
+                for (int flags = 0; flags < 4; ++flags) {
+                    PairShape s; s.refLen = s.qryLen = 10; s.refNum = counts[c][0]; s.qryNum = counts[c][1]; s.lowQ_r = flags & 1; s.lowQ_q = flags & 2;
+                    const bool want = task == 0 && c != 2 && flags != 0;      // (the flag may sit on the singleton or on the other side: :137 asks for either)
+                    ok = ok && deferredLowQuality(task, s) == want;
+                }
+        CHECK("policy_deferred_low_quality", ok);
+        // :108-115,121-124 and the retry loop of :95-129: task 0 defers errorType 1 and 2; errorType 3, and a failure left after the retries of tasks 1 and 2, end the run
+        const FailedPair P_ = FailedPair::Pass, D_ = FailedPair::Defer, F_ = FailedPair::Fatal;
+        const FailedPair want[3][4] = {{P_, D_, D_, F_}, {P_, F_, F_, F_}, {P_, F_, F_, F_}};
+        ok = true;
+        for (int task = 0; task < 3; ++task)
+            for (int e = 0; e < 4; ++e) ok = ok && failedPairVerdict(task, (int16_t)e) == want[task][e];
+        CHECK("policy_failed_pair_verdict", ok && !deferFailedPair(0, 0) && deferFailedPair(0, 1) && deferFailedPair(0, 2) && !deferFailedPair(2, 0));
+        // :116-129 from xdrop 5000, fLen 4096 (Talco_xdrop::Params for gap-extend -5).  errorType 1: xdrop * 2, fLen = min(int(xdrop * 4) << 1, minLen);
+        // errorType 2: fLen = min(int(fLen * 1.2) << 1, minLen)
+        auto start = [] { twl_params t{}; t.xdrop = 5000; t.flen = 4096; return t; };
+        {
+            const int32_t big = 1 << 30;
+            twl_params a = start();
+            nextRetryParams(1, big, a); bool k = a.xdrop == 10000 && a.flen == 80000;
+            nextRetryParams(1, big, a); k = k && a.xdrop == 20000 && a.flen == 160000;
+            twl_params b = start();
+            nextRetryParams(2, big, b); k = k && b.xdrop == 5000 && b.flen == 9830;          // int(4915.2) << 1
+            nextRetryParams(2, big, b); k = k && b.xdrop == 5000 && b.flen == 23592;         // int(11796.0) << 1
+            CHECK("policy_next_retry_params_long_sides", k);
+            a = start();
+            nextRetryParams(1, 3000, a); k = a.xdrop == 10000 && a.flen == 3000;
+            nextRetryParams(1, 3000, a); k = k && a.xdrop == 20000 && a.flen == 3000;
+            b = start();
+            nextRetryParams(2, 3000, b); k = k && b.xdrop == 5000 && b.flen == 3000;         // min(9830, 3000)
+            nextRetryParams(2, 3000, b); k = k && b.xdrop == 5000 && b.flen == 3000;         // min(int(3600.0) << 1, 3000)
+            CHECK("policy_next_retry_params_min_len_3000", k);
+            // the loop: first DP ended with errorType 1; the attempts then end with 1, 2, 0
+            const int16_t script[3] = {1, 2, 0};
+            const int32_t wantX[3] = {10000, 20000, 20000}, wantF[3] = {80000, 160000, 384000};      // int(192000.0) << 1
+            int calls = 0;
+            twl_params t = start();
+            k = true;
+            retryUntilPassed(t, 1, big, [&](const twl_params &g) { k = k && calls < 3 && g.xdrop == wantX[calls] && g.flen == wantF[calls]; return script[calls++]; });
+            CHECK("policy_retry_loop_scripted", k && calls == 3 && t.xdrop == 20000 && t.flen == 384000);
+            calls = 0;
+            t = start();
+            retryUntilPassed(t, 2, 3000, [&](const twl_params &g) { ++calls; return (int16_t)(g.flen == 3000 ? 0 : 3); });
+            CHECK("policy_retry_loop_passes_at_once", calls == 1 && t.xdrop == 5000 && t.flen == 3000);
+        }
+        // the deal of a level's pairs (longest processing time first)
+        {
+            std::mt19937 rng(4711);
+            ok = true;
+            for (int parts : {1, 2, 3, 8}) {
+                const int n = 200;
+                std::vector<long long> cost(n);
+                std::vector<char> takes(n);
+                for (int i = 0; i < n; ++i) { cost[i] = (long long)(rng() % 20000); takes[i] = (rng() % 4) != 0; }
+                const std::vector<int> owner = dealPairs(cost, takes, parts);
+                std::vector<long long> load(parts, 0);
+                long long maxCost = 1;
+                for (int i = 0; i < n; ++i) {
+                    if (!takes[i]) continue;
+                    ok = ok && owner[i] >= 0 && owner[i] < parts;
+                    load[owner[i]] += std::max<long long>(cost[i], 1);
+                    maxCost = std::max(maxCost, cost[i]);
+                }
+                ok = ok && *std::max_element(load.begin(), load.end()) - *std::min_element(load.begin(), load.end()) <= maxCost;
+                ok = ok && dealPairs(cost, takes, parts) == owner;                          // every rank computes the same deal
+                std::vector<long long> other = cost;                                           // pairs that take no part weigh on nobody
+                for (int i = 0; i < n; ++i) if (!takes[i]) other[i] = 1000000;
+                const std::vector<int> owner2 = dealPairs(other, takes, parts);
+                for (int i = 0; i < n; ++i) if (takes[i]) ok = ok && owner2[i] == owner[i];
+            }
+            CHECK("policy_deal_pairs", ok);
+        }
     }
     return g_fail ? 1 : 0;
 }

@@ -61,21 +61,35 @@ void setShard(SequenceDB *database, const Shard &shard)
 const std::vector<LevelRecord> &levelRecords(SequenceDB *database) { return ctxOf(database).levels; }
 const LevelTotals &runTotals(SequenceDB *database) { return ctxOf(database).totals; }
 
-std::vector<int> dealPairs(const std::vector<long long> &cost, const std::vector<char> &takesPart, int parts)
+void die(const char *what, int rc)
 {
-    const int n = (int)cost.size();
-    std::vector<int> owner(n, 0);
-    if (parts <= 1) return owner;
-    std::vector<int> order;
-    for (int i = 0; i < n; ++i) if (takesPart[i]) order.push_back(i);
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return cost[x] > cost[y]; });
-    std::vector<long long> load(parts, 0);
-    for (int i : order) {
-        const int d = (int)(std::min_element(load.begin(), load.end()) - load.begin());
-        owner[i] = d;
-        load[d] += std::max<long long>(cost[i], 1);
-    }
-    return owner;
+    std::cerr << "ERROR: " << what << " failed (" << rc << "): " << twl_last_error() << '\n';
+    exit(1);
+}
+
+void refuseCpuOnly(Option *option)
+{
+    if (option->cpuOnly) { std::cerr << "ERROR: --cpu-only is not available: this build has no CPU alignment path.\n"; exit(1); }
+}
+
+void foldStats(LevelRecord &rec, const twl_stats &st)
+{
+    rec.band_cells += st.band_cells;
+    rec.relaunched += (uint64_t)st.n_relaunched;
+    if (rec.matrix_mode < 0) { rec.matrix_mode = st.matrix_mode; rec.speculative = st.speculative; memcpy(rec.kernel, st.kernel, sizeof rec.kernel); }
+    rec.mt_predicted += st.mt_tiles_predicted;
+    rec.mt_inline += st.mt_tiles_inline;
+}
+
+void closeLevel(RunCtx &ctx, LevelRecord &rec, double tStart, const std::vector<char> &deferred, std::vector<int> &fallbackPairs, NodePairVec &nodes,
+                SequenceDB *database, Option *option)
+{
+    for (int i = 0; i < (int)deferred.size(); ++i)
+        if (deferred[i]) fallbackPairs.push_back(i);
+    if (!fallbackPairs.empty()) alignment_helper::fallback2cpu(fallbackPairs, nodes, database, option);
+    rec.level_ms = nowMs() - tStart;
+    ctx.totals.pairs += (uint64_t)nodes.size(); ctx.totals.band_cells += rec.band_cells; ctx.totals.relaunched += rec.relaunched; ctx.totals.kernel_ms += rec.kernel_ms; ctx.totals.exchange_ms += rec.exchange_ms;
+    ctx.levels.push_back(rec);
 }
 
 // Block layout per rank: header {band cells u64, relaunched u64, kernel ms f64, reserved} then, for the rank's pairs in ascending
@@ -159,7 +173,6 @@ void exchangeFinalPaths(RunCtx &ctx, twl_store *store, int device, const twl_par
 {
     const Shard &sh = ctx.shard;
     const double t0 = nowMs();
-    auto die = [](const char *what, int rc) { std::cerr << "ERROR: " << what << " failed (" << rc << "): " << twl_last_error() << '\n'; exit(1); };
     constexpr uint64_t kBlockMagic = 0x54574C44ull << 32;      // "TWLD"
     const int n = (int)owner.size(), world = sh.world;
     std::vector<std::vector<int>> mine(world);
@@ -285,13 +298,6 @@ twl_params baseParams(Params &param)          // == Talco_xdrop::Params(msa::Par
     return tp;
 }
 
-void nextRetryParams(int16_t err, int32_t minLen, twl_params &tr)
-{
-    if (err == 3) { std::cout << "There might be some bugs in the code!\n"; exit(1); }
-    if (err == 2) tr.flen = std::min(static_cast<int32_t>(tr.flen * 1.2) << 1, minLen);
-    else { tr.xdrop = static_cast<int32_t>(tr.xdrop * 2); tr.flen = std::min(static_cast<int32_t>(tr.xdrop * 4) << 1, minLen); }
-}
-
 // Level staging: the flat arrays of the C ABI ([pair][2][stride][P] etc.), kept for the whole run and only ever grown.  Each
 // pair's profile and gap penalties are built in place in its slot (preparePair), so nothing is copied on the host and the pages
 // are faulted in once, by the threads that fill them.
@@ -361,14 +367,15 @@ static void runBatch(RunCtx &ctx, LevelRecord &rec, const twl_params &tp, const 
     ctx.totals.stage_ms += tCall - tStage;
     int rc = twl_align_batch(&tp, n, stride, g_stage.freq + (size_t)first * 2 * sl * P, g_stage.gop + (size_t)first * 2 * sl,
                              g_stage.gex + (size_t)first * 2 * sl, len.data(), num.data(), aln, alnLen.data(), err.data());
-    if (rc != TWL_OK) { std::cerr << "ERROR: twl_align_batch failed (" << rc << "): " << twl_last_error() << '\n'; exit(1); }
+    if (rc != TWL_OK) die("twl_align_batch", rc);
     ctx.totals.call_ms += nowMs() - tCall;
     double kms = 0, tms = 0;
     for (int dev : g_devices) {      // the devices of one call run concurrently: cells add up, times do not
         twl_stats st{};
-        if (twl_get_stats(dev, &st) == TWL_OK) { ctx.totals.nominal_cells += st.nominal_cells; rec.band_cells += st.band_cells; rec.relaunched += (uint64_t)st.n_relaunched; kms = std::max(kms, st.kernel_ms); tms = std::max(tms, st.total_ms);
-            if (rec.matrix_mode < 0) { rec.matrix_mode = st.matrix_mode; rec.speculative = st.speculative; memcpy(rec.kernel, st.kernel, sizeof rec.kernel); }
-            rec.mt_predicted += st.mt_tiles_predicted; rec.mt_inline += st.mt_tiles_inline; }
+        if (twl_get_stats(dev, &st) != TWL_OK) continue;
+        ctx.totals.nominal_cells += st.nominal_cells;
+        foldStats(rec, st);
+        kms = std::max(kms, st.kernel_ms); tms = std::max(tms, st.total_ms);
     }
     rec.kernel_ms += kms;
     ctx.totals.total_ms += tms;
@@ -381,12 +388,13 @@ static void runBatch(RunCtx &ctx, LevelRecord &rec, const twl_params &tp, const 
 
 void alignmentKernel_GPU(Tree *, NodePairVec &nodes, SequenceDB *database, Option *option, Params &param)
 {
-    if (option->cpuOnly) { std::cerr << "ERROR: --cpu-only is not available: this build has no CPU alignment path.\n"; exit(1); }
+    refuseCpuOnly(option);
     ensureInit(option);
     RunCtx &ctx = ctxOf(database);
+    const int task = database->currentTask;
     LevelRecord rec;
     rec.pairs = (int32_t)nodes.size();
-    rec.task = database->currentTask;
+    rec.task = task;
     const int n = (int)nodes.size();
     const int P = param.matrixSize + 1;
     std::vector<PairInputs> in(n);
@@ -395,7 +403,7 @@ void alignmentKernel_GPU(Tree *, NodePairVec &nodes, SequenceDB *database, Optio
     // wide levels: one pair per thread; narrow levels (upper tree): pairs in turn, the helpers' own column/sequence loops fan out
     const bool acrossPairs = n >= omp_get_max_threads();
     int stride = 1;
-    for (auto &pr : nodes) stride = std::max({stride, pr.first->getAlnLen(database->currentTask), pr.second->getAlnLen(database->currentTask)});
+    for (auto &pr : nodes) stride = std::max({stride, pr.first->getAlnLen(task), pr.second->getAlnLen(task)});
     g_stage.ensure((size_t)n, (size_t)stride, (size_t)P);
     const size_t sl = (size_t)stride;
 #pragma omp parallel for schedule(dynamic, 1) if (acrossPairs)
@@ -407,67 +415,51 @@ void alignmentKernel_GPU(Tree *, NodePairVec &nodes, SequenceDB *database, Optio
 
     std::vector<alnPath> paths(n);
     std::vector<int16_t> errs(n, 0);
-    // pairs that go to the DP, grouped by gapCharScore (alignment-cpu.cpp:88); with several processes each aligns the pairs dealt to it
+    // pairs that go to the DP, grouped by gapCharScore (level_policy.hpp); with several processes each aligns the pairs dealt to it
     std::vector<char> takesPart(n, 0);
     std::vector<long long> cost(n, 0);
     for (int i = 0; i < n; ++i) {
-        if (in[i].refLen == 0) paths[i].assign(in[i].qryLen, 1);                              // :89-90
-        if (in[i].qryLen == 0) paths[i].insert(paths[i].end(), in[i].refLen, 2);
-        if (!paths[i].empty() || in[i].lowQ_r || in[i].lowQ_q) continue;                       // :93,95
+        paths[i] = trivialPath(in[i]);
+        if (!goesToDp(in[i])) continue;
         takesPart[i] = 1;
         cost[i] = (long long)in[i].lens.first + in[i].lens.second;
     }
     const std::vector<int> owner = dealPairs(cost, takesPart, ctx.shard.world);
     std::vector<int> plain, zeroGap;
-    auto zeroGapPair = [&](int i) { return database->currentTask == 1 || database->currentTask == 2 || in[i].refNum > 10000 || in[i].qryNum > 10000; };
     for (int i = 0; i < n; ++i)
-        if (takesPart[i] && owner[i] == ctx.shard.rank) (zeroGapPair(i) ? zeroGap : plain).push_back(i);
+        if (takesPart[i] && owner[i] == ctx.shard.rank) (zeroGapChar(task, in[i]) ? zeroGap : plain).push_back(i);
     twl_params tp = baseParams(param);
     runBatch(ctx, rec, tp, plain, in, P, stride, paths, errs);
     twl_params tz = tp;
     tz.gap_char = 0;
     runBatch(ctx, rec, tz, zeroGap, in, P, stride, paths, errs);
 
-    // alignment-cpu.cpp:116-129: in the later tasks a failed pair is retried with a larger X-drop / band limit (by the rank that owns it)
-    if (database->currentTask != 0) {
-        for (int i = 0; i < n; ++i) {
-            if (!takesPart[i] || owner[i] != ctx.shard.rank || errs[i] == 0) continue;
-            twl_params tr = zeroGapPair(i) ? tz : tp;
-            const int minLen = std::min(in[i].lens.first, in[i].lens.second);
-            while (errs[i] != 0) {
-                nextRetryParams(errs[i], minLen, tr);
-                if (option->printDetail) std::cout << "Retry pair No. " << i << "\txdrop " << tr.xdrop << " flen " << tr.flen << '\n';
-                runBatch(ctx, rec, tr, std::vector<int>{i}, in, P, stride, paths, errs);
-            }
-        }
+    // in the later tasks a failed pair is retried with a larger X-drop / band limit, by the rank that owns it
+    for (int i = 0; task != 0 && i < n; ++i) {
+        if (!takesPart[i] || owner[i] != ctx.shard.rank) continue;
+        twl_params tr = zeroGapChar(task, in[i]) ? tz : tp;
+        retryUntilPassed(tr, errs[i], std::min(in[i].lens.first, in[i].lens.second), [&](const twl_params &grown) {
+            if (option->printDetail) std::cout << "Retry pair No. " << i << "\txdrop " << grown.xdrop << " flen " << grown.flen << '\n';
+            runBatch(ctx, rec, grown, std::vector<int>{i}, in, P, stride, paths, errs);
+            return errs[i];
+        });
     }
     exchangePaths(ctx, owner, takesPart, 2 * stride, paths, errs, rec);
 
-    // alignment-cpu.cpp:108-115: task 0 defers a failed pair
     std::vector<int> fallbackPairs;
-    for (int i = 0; i < n; ++i) {
-        if (errs[i] == 0) continue;
-        if (errs[i] == 3) { std::cout << "There might be some bugs in the code!\n"; exit(1); }
-        paths[i].clear();
-        fallbackPairs.push_back(i);
-    }
+    for (int i = 0; i < n; ++i)
+        if (deferFailedPair(task, errs[i])) { paths[i].clear(); fallbackPairs.push_back(i); }
 
     std::vector<char> deferred(n, 0);
     const double tFin = nowMs();
 #pragma omp parallel for schedule(dynamic, 1) if (acrossPairs)
     for (int i = 0; i < n; ++i) {                                                              // alignment-cpu.cpp:136-175
-        // low-quality singleton rule (:136-144): such a pair is deferred whatever the DP said
-        deferred[i] = (database->currentTask == 0 && (in[i].refNum == 1 || in[i].qryNum == 1) && (in[i].lowQ_r || in[i].lowQ_q)) ? 1 : 0;
+        deferred[i] = deferredLowQuality(task, in[i]) ? 1 : 0;      // (finishPair drops such a pair's path by the same rule)
         finishPair(nodes[i], database, option, param, in[i], paths[i]);
         in[i] = PairInputs();                                                                   // release the profile buffers early
     }
     ctx.totals.finish_ms += nowMs() - tFin;
-    for (int i = 0; i < n; ++i)
-        if (deferred[i]) fallbackPairs.push_back(i);
-    if (!fallbackPairs.empty()) alignment_helper::fallback2cpu(fallbackPairs, nodes, database, option);
-    rec.level_ms = nowMs() - tPrep;
-    ctx.totals.pairs += (uint64_t)n; ctx.totals.band_cells += rec.band_cells; ctx.totals.relaunched += rec.relaunched; ctx.totals.kernel_ms += rec.kernel_ms; ctx.totals.exchange_ms += rec.exchange_ms;
-    ctx.levels.push_back(rec);
+    closeLevel(ctx, rec, tPrep, deferred, fallbackPairs, nodes, database, option);
     if (option->printDetail)
         std::cerr << "  phases (ms): prepare " << ctx.totals.prepare_ms - before.prepare_ms << " stage " << ctx.totals.stage_ms - before.stage_ms << " call "
                   << ctx.totals.call_ms - before.call_ms << " (kernel " << ctx.totals.kernel_ms - before.kernel_ms << ") finish " << ctx.totals.finish_ms - before.finish_ms

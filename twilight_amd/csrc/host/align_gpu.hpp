@@ -24,8 +24,16 @@ struct RunCtx {
     struct Raw { char *p = nullptr; size_t cap = 0; bool pinned = false; char *get(size_t n); ~Raw(); Raw() = default; Raw(Raw &&o) noexcept : p(o.p), cap(o.cap), pinned(o.pinned) { o.p = nullptr; o.cap = 0; } Raw(const Raw &) = delete; };      // grow-only, never zero-filled host buffer
     ~RunCtx();
 };
-// Longest-processing-time deal of a level's pairs to `parts` owners (deterministic: every rank computes the same answer).
-std::vector<int> dealPairs(const std::vector<long long> &cost, const std::vector<char> &takesPart, int parts);
+// (the level policy both kernels follow -- which pairs go to the DP, retry, defer, the deal of the pairs to owners -- is level_policy.hpp)
+[[noreturn]] void die(const char *what, int rc);      // "ERROR: <what> failed (<rc>): <twl_last_error()>", exit 1
+void refuseCpuOnly(Option *option);                   // --cpu-only ends the run: there is no CPU alignment path
+// What one twl_stats (a device's last DP call) adds to a level's record: cells, relaunched pairs, tile counts, and once the kernel's
+// identity.  The times stay with the caller: devices run concurrently, so they combine by max, not by sum.
+void foldStats(LevelRecord &rec, const twl_stats &st);
+// The end of a level in both kernels: the deferred pairs join the failed ones and go to fallback2cpu, the record gets the level's time
+// and joins the run's totals and records.  (Each kernel prints its own -v "phases" line after it.)
+void closeLevel(RunCtx &ctx, LevelRecord &rec, double tStart, const std::vector<char> &deferred, std::vector<int> &fallbackPairs, NodePairVec &nodes,
+                SequenceDB *database, Option *option);
 // All-gather of the paths the ranks aligned: on return paths/errs hold every pair of the level on every rank.
 void exchangePaths(RunCtx &ctx, const std::vector<int> &owner, const std::vector<char> &takesPart, int pathCap, std::vector<alnPath> &paths,
                    std::vector<int16_t> &errs, LevelRecord &rec);
@@ -39,10 +47,6 @@ void exchangeFinalPaths(RunCtx &ctx, twl_store *store, int device, const twl_par
                         LevelRecord &rec);
 const std::vector<int> &selectedDevices();
 twl_params baseParams(Params &param);          // == Talco_xdrop::Params(msa::Params&), TALCO-XDrop.cpp:36-53
-// alignment-cpu.cpp:116-129 (tasks other than 0 retry a failed pair until it passes): the X-drop and band limit of the next attempt after a DP
-// that ended with errorType err (1: xdrop doubles, 2: the band limit grows), minLen = the shorter side after gappy-column removal.
-// errorType 3 ends the run, as it does there.
-void nextRetryParams(int16_t err, int32_t minLen, twl_params &tr);
 // Consensus string and removed-column runs of one side from the column info of twl_level_prepare (letters: "ACGTN" / the 20 acids + 'X').
 void runsAndConsensus(const uint8_t *info, int len, bool removal, const char *letters, IntPairVec &runs, std::string &cons);
 inline double nowMs() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }

@@ -43,12 +43,6 @@ struct Reader {
     void need(size_t k) const { if (at + k > n) { std::cerr << "ERROR: malformed subtree block from another rank.\n"; exit(1); } }
 };
 
-void die(const char *what, int rc)
-{
-    std::cerr << "ERROR: " << what << " failed (" << rc << "): " << twl_last_error() << '\n';
-    exit(1);
-}
-
 // all-gather of byte strings of different lengths: sizes first, then the strings padded to the longest
 std::vector<std::vector<char>> allGatherBlobs(RunCtx &ctx, const std::vector<char> &mine)
 {

@@ -18,6 +18,9 @@
 // construction, cached profiles included); only the DP -- the 99 % -- is sharded: each device aligns its share of the pairs
 // (twl_level_align with a mask, longest-processing-time deal), the paths meet on the host, and every device commits all of them.
 // Per level only paths cross PCIe, nothing crosses xGMI.  --test-virtual-devices k (tests) runs k replicas on the first device.
+//
+// A level in steps (alignmentKernel_Resident at the end of the file drives them): describeLevel, prepareOnReplicas, fetchColumnInfo, planDp,
+// alignShare per replica, mergeShares, joinHandedBack, exchange, judgeFailures, finalPathsOnHost, commitAndBookkeep, closeLevel.
 #include "align_gpu.hpp"
 
 #include <cstring>
@@ -37,18 +40,12 @@ namespace gpu {
 namespace {
 
 // the per-run state (store replicas, cache ids, totals) lives in RunCtx (align_gpu.hpp), reached through the SequenceDB
-inline twl_store *firstStore(RunCtx &ctx) { return ctx.stores.empty() ? nullptr : ctx.stores[0]; }
+inline twl_store *firstStore(const RunCtx &ctx) { return ctx.stores.empty() ? nullptr : ctx.stores[0]; }
 
 // Grow-only, never zero-filled staging shared by the runs of a process (one run aligns at a time): a level of 3 000 pairs x 10 kbp
 // moves ~70 MB per array and first-touch page faults cost more than the copies.
 std::vector<RunCtx::Raw> g_alnStage;      // per replica: paths as the DP wrote them
 RunCtx::Raw g_finalStage, g_infoStage;    // final paths as the commit reads them; column info
-
-void die(const char *what, int rc)
-{
-    std::cerr << "ERROR: " << what << " failed (" << rc << "): " << twl_last_error() << '\n';
-    exit(1);
-}
 
 void createStore(RunCtx &ctx, SequenceDB *db, Option *option)
 {
@@ -145,13 +142,443 @@ void materialise(Tree *T, SequenceDB *db, Option *option)
     if (option->printDetail) std::cerr << "Rows back on the host in " << nowMs() - t0 << " ms\n";
 }
 
-struct PairState {
-    int32_t refLen, qryLen, refNum, qryNum;
-    IntPair lens;
-    bool lowQ_r, lowQ_q;
+// Column info of one pair for addGappyColumnsBack: removed-column runs and consensus of the two sides.
+struct ColumnInfo {
     std::pair<IntPairVec, IntPairVec> gappy;
     stringPair consensus;
 };
+
+// How the paths of a level travel, from the shard and the replica count.  inPlace and devX hold for ONE replica only (nd == 1 in every
+// term): twl_level_restore, the pairs it hands back and the HBM-to-HBM exchange never meet a second replica thread.
+struct PathRoute { bool procs, devX, inPlace; };
+PathRoute routeOf(const Shard &sh, int nd)
+{
+    PathRoute r;
+    // One device, one process: the paths never leave HBM -- pairs that lost no column commit their DP path as it is, the others get their
+    // columns back on the device (twl_level_restore); the column info comes to the host only for a pair the device hands back (below).
+    r.procs = sh.world > 1;
+    // ... and so it is with several processes when they can all-gather device blocks (Shard::exchangeDev): each rank restores its own
+    // pairs on its device, the final paths travel HBM to HBM (exchangeFinalPaths below), every rank commits all of them from HBM.
+    r.devX = (nd == 1 && (sh.exchangeDev != nullptr || sh.rccl));
+    r.inPlace = (nd == 1 && ((!r.procs && !sh.exchange && !sh.rccl) || r.devX));
+    return r;
+}
+
+const char kBases[] = {'A', 'C', 'G', 'T', 'N'};
+const char kAcids[] = {'A', 'C', 'D', 'E', 'F', 'G', 'H', 'I', 'K', 'L', 'M', 'N', 'P', 'Q', 'R', 'S', 'T', 'V', 'W', 'Y', 'X'};
+
+// One level.  The steps below fill it in turn on the calling thread (each group of members names its step); the replica threads of
+// alignShare get it const.  Steps that change the run or the nodes take RunCtx / NodePairVec as an argument of their own.
+struct Level {
+    const RunCtx &ctx;
+    const NodePairVec &nodes;
+    SequenceDB *database;
+    Option *option;
+    Params &param;
+    int task, n, nd;                              // nd: device replicas of this process
+    const char *letters;                          // consensus letter of a column-info code
+    bool removal;
+    PathRoute route;
+    twl_params tp, tz;                            // tz: gapCharScore 0
+    // describeLevel
+    std::vector<twl_side> sides;
+    std::vector<PairShape> ps;
+    std::vector<int32_t> members;
+    std::vector<float> weights;
+    int stride = 1;                               // row pitch of the profiles: the longest side
+    int pathStride = 1;                           // row pitch of the final paths: refLen + qryLen before removal bounds every path
+    // prepareOnReplicas
+    std::vector<int> needInfo;                    // pairs that lost a column
+    std::vector<char> needsHost;                  // ... as a flag per pair
+    // planDp
+    std::vector<uint8_t> maskZero;                // pairs of the DP that take gapCharScore 0
+    std::vector<char> takesPart;                  // pairs of the DP
+    std::vector<int> owner;
+    int meBase = 0;                               // replica d of this process aligns the pairs of owner meBase + d
+    Level(const RunCtx &c, const NodePairVec &nv, SequenceDB *db, Option *o, Params &p)
+        : ctx(c), nodes(nv), database(db), option(o), param(p), task(db->currentTask), n((int)nv.size()), nd((int)c.stores.size()),
+          letters(o->type == 'n' ? kBases : kAcids), removal(!(o->gappyVertical == 1.0)), route(routeOf(c.shard, nd)), tp(baseParams(p)), tz(tp)
+    {
+        tz.gap_char = 0;
+    }
+};
+
+// What the DP and the steps after it leave per pair.  While the replicas run (alignShare), row i of paths / errs / fromDp / dpLen is
+// written in place by the replica that owns pair i and by nobody else; before and after that only the calling thread touches the rows.
+struct PairRows {
+    std::vector<alnPath> paths;
+    std::vector<int16_t> errs;
+    std::vector<uint8_t> fromDp;                  // 1: the DP path is the final path; 2: twl_level_restore made the final path, in HBM
+    std::vector<int32_t> dpLen;
+    std::vector<ColumnInfo> cols;                 // calling thread only
+    explicit PairRows(int n) : paths(n), errs(n, 0), fromDp(n, 0), dpLen(n, 0), cols(n) {}
+};
+
+// What one replica reports besides the rows of its pairs; merged into the level on the calling thread (mergeShares).
+struct ReplicaShare {
+    double callMs = 0, totMs = 0;
+    LevelRecord part;                             // its cells, relaunched pairs, kernel time and kernel identity
+    uint64_t nominalCells = 0;
+    std::vector<int32_t> handedBack, handedBackLen;      // in-place mode: pairs twl_level_restore handed back to the host, and their DP path lengths
+};
+
+// ---- side descriptors (what calculateProfile reads from the two nodes, alignment-helper.cpp:8-40) ----
+void describeLevel(Level &lv, RunCtx &ctx, NodePairVec &nodes)
+{
+    const int n = lv.n;
+    SequenceDB *database = lv.database;
+    Option *option = lv.option;
+    std::vector<twl_side> &sides = lv.sides;
+    sides.resize(2 * (size_t)n);
+    lv.ps.resize(n);
+    size_t nMembers = 0;
+    // (what is read from the nodes and sequences of a pair -- cache misses, mostly -- in parallel; the running member offsets and the
+    // ids of newly cached profiles, which depend on the order of the pairs, in a serial pass behind it)
+#pragma omp parallel for schedule(static) if (n >= 512)
+    for (int i = 0; i < n; ++i) {
+        Node *nd[2] = {nodes[i].first, nodes[i].second};
+        PairShape &s = lv.ps[i];
+        s.refLen = nd[0]->getAlnLen(0); s.qryLen = nd[1]->getAlnLen(0);
+        s.refNum = nd[0]->getAlnNum(0); s.qryNum = nd[1]->getAlnNum(0);
+        for (int sd = 0; sd < 2; ++sd) {
+            twl_side &x = sides[2 * (size_t)i + sd];
+            x.n_members = (int32_t)nd[sd]->seqsIncluded.size();
+            x.len = sd ? s.qryLen : s.refLen;
+            x.num = sd ? s.qryNum : s.refNum;
+            x.weight = nd[sd]->alnWeight;
+            x.cache_id = nd[sd]->cacheId;
+            x.store_id = -1;
+            x.reserved = 0;
+        }
+        s.lowQ_r = lowQualitySide(option->alnMode == MERGE_MSA, s.refNum, firstSeqLowQuality(nd[0], database));
+        s.lowQ_q = lowQualitySide(option->alnMode == MERGE_MSA, s.qryNum, firstSeqLowQuality(nd[1], database));
+    }
+    for (int i = 0; i < n; ++i) {
+        const PairShape &s = lv.ps[i];
+        Node *nd[2] = {nodes[i].first, nodes[i].second};
+        const bool storeFreq = (s.refNum >= option->calProfileTh || s.qryNum >= option->calProfileTh) || (sides[2 * (size_t)i].cache_id >= 0 || sides[2 * (size_t)i + 1].cache_id >= 0);
+        for (int sd = 0; sd < 2; ++sd) {
+            twl_side &x = sides[2 * (size_t)i + sd];
+            x.member_off = (int32_t)nMembers;
+            if (storeFreq && x.cache_id < 0) x.store_id = nd[sd]->cacheId = ctx.nextCacheId++;
+            nMembers += (size_t)x.n_members;
+            lv.stride = std::max(lv.stride, x.len);
+        }
+        lv.pathStride = std::max(lv.pathStride, s.refLen + s.qryLen);
+    }
+    lv.members.resize(nMembers);
+    lv.weights.resize(nMembers);
+    // (levels of a few pairs stay on this thread: a parallel region of one iteration wakes every worker, and their spinning at its end
+    // slowed the serial stretches that follow -- 1.3 ms against 0.3 ms for the 100 000 members of a top level)
+#pragma omp parallel for schedule(dynamic, 16) if (n >= 64)
+    for (int i = 0; i < n; ++i) {
+        Node *nd[2] = {nodes[i].first, nodes[i].second};
+        for (int sd = 0; sd < 2; ++sd) {
+            const twl_side &x = sides[2 * (size_t)i + sd];
+            const float groupWeight = nd[sd]->alnWeight;
+            for (int m = 0; m < x.n_members; ++m) {
+                const int sIdx = nd[sd]->seqsIncluded[m];
+                if (sIdx < 0) { std::cerr << "ERROR: compressed sequence group in device-resident mode.\n"; exit(1); }
+                lv.members[x.member_off + m] = sIdx;
+                lv.weights[x.member_off + m] = database->sequences[sIdx]->weight / groupWeight * x.num;     // alignment-helper.cpp:27
+            }
+        }
+    }
+}
+
+// ---- device: profiles, consensus, gappy-column removal, gap penalties ----
+void prepareOnReplicas(Level &lv, RunCtx &ctx)
+{
+    const int n = lv.n;
+    std::vector<int32_t> lens(2 * (size_t)n);
+    std::vector<std::vector<int32_t>> lensOf(lv.nd);
+    onAllStores(ctx, "twl_level_prepare", [&](int d) {
+        lensOf[d].resize(2 * (size_t)n);       // every replica prepares the whole level; column info is fetched from the first only
+        return twl_level_prepare(ctx.stores[d], &lv.tp, lv.option->gappyVertical, n, lv.sides.data(), lv.members.data(), lv.weights.data(), lv.stride,
+                                 d == 0 ? lens.data() : lensOf[d].data(), nullptr);
+    });
+    for (int d = 1; d < lv.nd; ++d)
+        if (lensOf[d] != lens) { std::cerr << "ERROR: device replicas disagree on the prepared level.\n"; exit(1); }
+    // The column info (consensus letter + gappy flag per original column) only matters for addGappyColumnsBack, i.e. for pairs in
+    // which some column was removed: fetch it for those (at the leaf level none: single sequences have no gap columns).
+    lv.needsHost.assign(n, 0);
+    for (int i = 0; i < n; ++i) {
+        PairShape &s = lv.ps[i];
+        s.lens = {lens[2 * i], lens[2 * i + 1]};
+        if (s.lens.first != s.refLen || s.lens.second != s.qryLen) { lv.needInfo.push_back(i); lv.needsHost[i] = 1; }
+    }
+}
+
+// Consensus + removed runs of the pairs `which` into cols, one synchronisation: the level's whole block (most pairs need it) or their
+// blocks only.  Calling thread only: the stage is process-wide.
+void fetchColumnInfo(const Level &lv, const std::vector<int> &which, bool wholeBlock, std::vector<ColumnInfo> &cols)
+{
+    if (which.empty()) return;
+    const size_t stride = (size_t)lv.stride;
+    uint8_t *info = reinterpret_cast<uint8_t *>(g_infoStage.get(2 * (wholeBlock ? (size_t)lv.n : which.size()) * stride));
+    const int rc = wholeBlock ? twl_level_read_colinfo(firstStore(lv.ctx), -1, 0, info)
+                              : twl_level_read_colinfo_many(firstStore(lv.ctx), (int32_t)which.size(), which.data(), info);
+    if (rc != TWL_OK) die(wholeBlock ? "twl_level_read_colinfo" : "twl_level_read_colinfo_many", rc);
+#pragma omp parallel for schedule(dynamic, 4)
+    for (int t = 0; t < (int)which.size(); ++t) {
+        const int i = which[t];
+        const size_t slot = wholeBlock ? (size_t)i : (size_t)t;
+        runsAndConsensus(&info[2 * slot * stride], lv.ps[i].refLen, lv.removal, lv.letters, cols[i].gappy.first, cols[i].consensus.first);
+        runsAndConsensus(&info[(2 * slot + 1) * stride], lv.ps[i].qryLen, lv.removal, lv.letters, cols[i].gappy.second, cols[i].consensus.second);
+    }
+}
+
+// ---- DP with the reference's grouping and retry/defer policy (level_policy.hpp) ----
+void planDp(Level &lv, PairRows &rows)
+{
+    const int n = lv.n;
+    lv.maskZero.assign(n, 0);
+    lv.takesPart.assign(n, 0);
+    std::vector<long long> cost(n, 0);
+    for (int i = 0; i < n; ++i) {
+        const PairShape &s = lv.ps[i];
+        rows.paths[i] = trivialPath(s);
+        cost[i] = (long long)s.lens.first + s.lens.second;
+        if (!goesToDp(s)) continue;
+        lv.takesPart[i] = 1;
+        lv.maskZero[i] = zeroGapChar(lv.task, s) ? 1 : 0;
+    }
+    // deal the pairs, longest first (cost ~ R + Q after gappy-column removal), to the device replicas of this process or, with several
+    // processes (one device each), to the ranks; everybody aligns its share
+    lv.owner = dealPairs(cost, lv.takesPart, lv.route.procs ? lv.ctx.shard.world : lv.nd);
+    lv.meBase = lv.route.procs ? lv.ctx.shard.rank : 0;
+}
+
+// The counters of the DP call replica d has just made, into its share.
+void addStats(const Level &lv, int d, bool firstCall, ReplicaShare &mine)
+{
+    // per-device counters (virtual replicas share one device, whose counters describe the last call of any of them: left out)
+    const bool ownDevice = lv.nd == 1 || lv.ctx.storeDev[d] != lv.ctx.storeDev[(d + 1) % lv.nd];
+    const bool nominal = firstCall && d == 0;      // (R*Q of the level's pairs, once: the classic GCUPS figure of bench.py)
+    twl_stats st{};
+    if ((!ownDevice && !nominal) || twl_get_stats(lv.ctx.storeDev[d], &st) != TWL_OK) return;
+    if (ownDevice) { foldStats(mine.part, st); mine.part.kernel_ms += st.kernel_ms; mine.totMs += st.total_ms; }
+    if (nominal) mine.nominalCells += st.nominal_cells;
+}
+
+// In the deferred pass a failed pair is retried, by whoever owns it, with a larger X-drop / band limit until it passes.
+int retryDeferredPair(const Level &lv, int d, const std::vector<uint8_t> &mask, int8_t *aln, std::vector<int32_t> &alnLen, std::vector<int16_t> &err, ReplicaShare &mine)
+{
+    // a retry is a call of the whole level with a one-pair mask, and a DP call zero-fills the outputs of ALL the level's pairs: with more
+    // than one pair it would wipe what the others have just produced.  The deferred pass aligns one profile per level
+    // (progressive.cpp:283-291); a task-1 level of several pairs is refused up front -- whether or not a pair fails -- rather than silently
+    // wrong or dependent on the data (the limit is part of the contract: include/twl_msa.h)
+    if (lv.n != 1) { std::cerr << "ERROR: a deferred-pass (task 1) level must hold exactly one pair; this one has " << lv.n << ".\n"; return (int)TWL_ERR_UNSUPPORTED; }
+    if (!mask[0]) return (int)TWL_OK;
+    twl_params tr = lv.maskZero[0] ? lv.tz : lv.tp;
+    const uint8_t one = 1;
+    int rc = TWL_OK;
+    retryUntilPassed(tr, err[0], std::min(lv.ps[0].lens.first, lv.ps[0].lens.second), [&](const twl_params &grown) {
+        if (lv.option->printDetail) std::cout << "Retry pair No. " << 0 << "\txdrop " << grown.xdrop << " flen " << grown.flen << '\n';
+        const double tRetry = nowMs();
+        rc = twl_level_align(lv.ctx.stores[d], &grown, &one, aln, alnLen.data(), err.data());
+        if (rc != TWL_OK) return (int16_t)0;      // (ends the loop; the caller stops the run on rc)
+        mine.callMs += nowMs() - tRetry;
+        addStats(lv, d, false, mine);
+        return err[0];
+    });
+    return rc;
+}
+
+// The results of replica d's pairs, sorted into: final in HBM as the DP wrote it / columns restored on the device / handed back to the host
+// (in-place mode), or copied out of the replica's staging (otherwise).
+int sortResults(const Level &lv, int d, const std::vector<uint8_t> &mask, const int8_t *aln, const std::vector<int32_t> &alnLen, const std::vector<int16_t> &err,
+                PairRows &rows, ReplicaShare &mine)
+{
+    const size_t pitch = (size_t)2 * lv.stride;
+    std::vector<int32_t> restore, restoreLen;
+    for (int i = 0; i < lv.n; ++i) {
+        if (!mask[i]) continue;
+        rows.errs[i] = err[i];
+        const int32_t len = (err[i] == 0) ? alnLen[i] : 0;
+        if (!lv.route.inPlace) rows.paths[i].assign(&aln[i * pitch], &aln[i * pitch] + len);
+        else if (lv.needsHost[i]) {
+            // (a low-quality singleton is deferred in finalPathsOnHost: its path is dropped)
+            if (len > 0 && !deferredLowQuality(lv.task, lv.ps[i])) { restore.push_back(i); restoreLen.push_back(len); } else rows.paths[i].clear();
+        }
+        else if (len > 0) { rows.fromDp[i] = 1; rows.dpLen[i] = len; }
+    }
+    if (restore.empty()) return (int)TWL_OK;
+    std::vector<int32_t> fin(restore.size(), -1);      // gappy columns back on the device: these paths never leave HBM either
+    const int rc = twl_level_restore(lv.ctx.stores[d], &lv.tp, (int32_t)restore.size(), restore.data(), lv.pathStride, fin.data());
+    if (rc != TWL_OK) return rc;
+    for (size_t t = 0; t < restore.size(); ++t) {
+        if (fin[t] > 0) { rows.fromDp[restore[t]] = 2; rows.dpLen[restore[t]] = fin[t]; }
+        else { mine.handedBack.push_back(restore[t]); mine.handedBackLen.push_back(restoreLen[t]); }      // a two-sided run too large for the device: on the host, as before
+    }
+    return (int)TWL_OK;
+}
+
+// The share of replica d, on its own thread: launch, deferred-pass retry, results into the rows of its pairs.
+int alignShare(const Level &lv, int d, PairRows &rows, ReplicaShare &mine)
+{
+    // ONE launch for the pairs of both gap-character kinds (alignment-cpu.cpp:88 decides per pair; until round 4 one call per kind, which
+    // doubled the latency of the top levels of a 100 000-leaf tree, where a few pairs of each kind meet)
+    const int n = lv.n;
+    std::vector<uint8_t> mask(n, 0);
+    int cnt = 0, cntZero = 0;
+    for (int i = 0; i < n; ++i) if (lv.takesPart[i] && lv.owner[i] == lv.meBase + d) { mask[i] = 1; ++cnt; cntZero += lv.maskZero[i]; }
+    if (!cnt) return (int)TWL_OK;
+    int8_t *aln = lv.route.inPlace ? nullptr : reinterpret_cast<int8_t *>(g_alnStage[d].get((size_t)n * 2 * lv.stride));
+    std::vector<int32_t> alnLen(n);
+    std::vector<int16_t> err(n);
+    const double tCall = nowMs();
+    const int rc = (cntZero == cnt) ? twl_level_align(lv.ctx.stores[d], &lv.tz, mask.data(), aln, alnLen.data(), err.data())
+                                    : twl_level_align_mixed(lv.ctx.stores[d], &lv.tp, mask.data(), cntZero ? lv.maskZero.data() : nullptr, aln, alnLen.data(), err.data());
+    if (rc != TWL_OK) return rc;
+    mine.callMs += nowMs() - tCall;
+    addStats(lv, d, true, mine);
+    if (lv.task == 1) {
+        const int rr = retryDeferredPair(lv, d, mask, aln, alnLen, err, mine);
+        if (rr != TWL_OK) return rr;
+    }
+    return sortResults(lv, d, mask, aln, alnLen, err, rows, mine);
+}
+
+#ifdef TWL_DEV      // development builds: one line per pair for tools/sim_schedule.py
+void dumpSchedule(const Level &lv, const PairRows &rows)
+{
+    const char *dump = getenv("TWL_DUMP_SCHEDULE");
+    FILE *f = dump ? fopen(dump, "a") : nullptr;
+    if (!f) return;
+    std::vector<uint64_t> pc(lv.n, 0);
+    if (lv.nd == 1) (void)twl_get_pair_cells(lv.ctx.storeDev[0], pc.data(), lv.n);
+    for (int i = 0; i < lv.n; ++i)
+        fprintf(f, "%d %d %d %d %d %d %d %llu\n", (int)lv.ctx.levels.size(), i, lv.nodes[i].first->seqsIncluded.empty() ? -1 : lv.nodes[i].first->seqsIncluded[0],
+                lv.nodes[i].second->seqsIncluded.empty() ? -1 : lv.nodes[i].second->seqsIncluded[0], lv.ps[i].lens.first, lv.ps[i].lens.second, (int)rows.errs[i], (unsigned long long)pc[i]);
+    fclose(f);
+}
+#endif
+
+// The replicas ran concurrently: times combine by max, counts add up; the kernel's identity and the tile counts are replica 0's.
+void mergeShares(const std::vector<ReplicaShare> &shares, RunCtx &ctx, LevelRecord &rec)
+{
+    double callMs = 0, totMs = 0;
+    for (const ReplicaShare &s : shares) {
+        callMs = std::max(callMs, s.callMs); totMs = std::max(totMs, s.totMs);
+        rec.kernel_ms = std::max(rec.kernel_ms, s.part.kernel_ms);
+        rec.band_cells += s.part.band_cells;
+        rec.relaunched += s.part.relaunched;
+    }
+    const LevelRecord &p0 = shares[0].part;
+    rec.matrix_mode = p0.matrix_mode; rec.speculative = p0.speculative; memcpy(rec.kernel, p0.kernel, sizeof rec.kernel);
+    rec.mt_predicted += p0.mt_predicted; rec.mt_inline += p0.mt_inline;
+    ctx.totals.call_ms += callMs;
+    ctx.totals.total_ms += totMs;
+    ctx.totals.nominal_cells += shares[0].nominalCells;
+}
+
+// gappy columns back on the host for one pair (alignment-helper.cpp:324-375)
+void restoreOnHost(const Level &lv, PairRows &rows, int i, alnPath &full)
+{
+    const PairShape &s = lv.ps[i];
+    int alnRef = 0, alnQry = 0;
+    for (auto a : rows.paths[i]) { if (a != 1) ++alnRef; if (a != 2) ++alnQry; }
+    alignment_helper::addGappyColumnsBack(rows.paths[i], full, rows.cols[i].gappy, lv.param, {alnRef, alnQry}, rows.cols[i].consensus);
+    alnRef = alnQry = 0;
+    for (auto a : full) { if (a != 1) ++alnRef; if (a != 2) ++alnQry; }
+    if (alnRef != s.refLen) std::cout << "R: Post " << lv.nodes[i].first->identifier << "(" << alnRef << "/" << s.refLen << ")\n";
+    if (alnQry != s.qryLen) std::cout << "Q: Post " << lv.nodes[i].second->identifier << "(" << alnQry << "/" << s.qryLen << ")\n";
+    if ((int)full.size() > lv.pathStride) { std::cerr << "ERROR: path longer than both profiles together.\n"; exit(1); }
+}
+
+// (rare: a two-sided run too large for the device) the pairs the device handed back: their column info and DP paths come to the host,
+// the host puts the columns back and its result joins the others in HBM.  In-place mode only, hence one replica: share 0.
+void joinHandedBack(const Level &lv, const ReplicaShare &share, PairRows &rows)
+{
+    const std::vector<int32_t> &fetch = share.handedBack;
+    if (fetch.empty()) return;
+    if (!lv.route.inPlace) { std::cerr << "ERROR: pairs handed back to the host outside the in-place mode.\n"; exit(1); }
+    const size_t pitch = (size_t)2 * lv.stride;
+    fetchColumnInfo(lv, std::vector<int>(fetch.begin(), fetch.end()), false, rows.cols);
+    int8_t *blk = reinterpret_cast<int8_t *>(g_alnStage[0].get(fetch.size() * pitch));
+    int rc = twl_level_read_paths(firstStore(lv.ctx), (int32_t)fetch.size(), fetch.data(), share.handedBackLen.data(), blk, (int32_t)pitch);
+    if (rc != TWL_OK) die("twl_level_read_paths", rc);
+    for (size_t t = 0; t < fetch.size(); ++t) {
+        const int i = fetch[t];
+        rows.paths[i].assign(&blk[t * pitch], &blk[t * pitch] + share.handedBackLen[t]);
+        if (rows.errs[i] != 0 || rows.paths[i].empty()) continue;
+        alnPath full;
+        restoreOnHost(lv, rows, i, full);
+        if ((rc = twl_level_write_final(firstStore(lv.ctx), i, full.data(), (int32_t)full.size())) != TWL_OK) die("twl_level_write_final", rc);
+        rows.fromDp[i] = 2; rows.dpLen[i] = (int32_t)full.size();
+        rows.paths[i].clear();
+    }
+}
+
+// Several processes: everybody gets every path -- HBM to HBM when the ranks can all-gather device blocks, through the host otherwise.
+void exchange(const Level &lv, RunCtx &ctx, PairRows &rows, LevelRecord &rec)
+{
+    if (!lv.route.devX) { exchangePaths(ctx, lv.owner, lv.takesPart, 2 * lv.stride, rows.paths, rows.errs, rec); return; }
+    std::vector<int32_t> bound(lv.n);
+    for (int i = 0; i < lv.n; ++i) bound[i] = lv.ps[i].refLen + lv.ps[i].qryLen;
+    exchangeFinalPaths(ctx, firstStore(ctx), ctx.storeDev[0], lv.tp, lv.owner, lv.takesPart, bound, lv.pathStride, rows.fromDp, rows.dpLen, rows.errs, rec);
+}
+
+// A failed pair of the main pass is deferred; anywhere else it ends the run (the deferred pass retried until errorType 0).
+std::vector<int> judgeFailures(const Level &lv, PairRows &rows)
+{
+    std::vector<int> fallbackPairs;
+    for (int i = 0; i < lv.n; ++i) {
+        if (!deferFailedPair(lv.task, rows.errs[i])) continue;
+        rows.paths[i].clear();
+        rows.fromDp[i] = 0;
+        fallbackPairs.push_back(i);
+    }
+    return fallbackPairs;
+}
+
+// ---- gappy columns back for the paths that are on the host; returns the level's final-path block (row pitch pathStride) ----
+int8_t *finalPathsOnHost(const Level &lv, PairRows &rows, std::vector<int32_t> &finalLen, std::vector<char> &deferred)
+{
+    const int n = lv.n, pathStride = lv.pathStride;
+    int8_t *finalPaths = reinterpret_cast<int8_t *>(g_finalStage.get((size_t)n * pathStride));
+    std::vector<int> onHost;                 // pairs whose final path the host still has to make (none in the in-place mode: their paths are in HBM)
+    for (int i = 0; i < n; ++i) {
+        deferred[i] = deferredLowQuality(lv.task, lv.ps[i]) ? 1 : 0;
+        if (deferred[i]) { rows.paths[i].clear(); rows.fromDp[i] = 0; }
+        if (rows.fromDp[i]) { finalLen[i] = rows.dpLen[i]; continue; }      // no column was removed: the DP path is the final path, and it is in HBM
+        if (!rows.paths[i].empty()) onHost.push_back(i);
+    }
+#pragma omp parallel for schedule(dynamic, 1) if (onHost.size() > 1)
+    for (int t = 0; t < (int)onHost.size(); ++t) {
+        const int i = onHost[t];
+        const ColumnInfo &c = rows.cols[i];
+        if (c.gappy.first.empty() && c.gappy.second.empty()) {      // nothing was removed: the DP path is the final path (addGappyColumnsBack would copy it)
+            if ((int)rows.paths[i].size() > pathStride) { std::cerr << "ERROR: path longer than both profiles together.\n"; exit(1); }
+            std::copy(rows.paths[i].begin(), rows.paths[i].end(), &finalPaths[(size_t)i * pathStride]);
+            finalLen[i] = (int32_t)rows.paths[i].size();
+            continue;
+        }
+        alnPath full;
+        restoreOnHost(lv, rows, i, full);
+        std::copy(full.begin(), full.end(), &finalPaths[(size_t)i * pathStride]);
+        finalLen[i] = (int32_t)full.size();
+    }
+    return finalPaths;
+}
+
+// ---- the write-back on every replica, then the Node bookkeeping ----
+void commitAndBookkeep(const Level &lv, RunCtx &ctx, NodePairVec &nodes, const int8_t *finalPaths, const std::vector<int32_t> &finalLen, const PairRows &rows)
+{
+    onAllStores(ctx, "twl_level_commit", [&](int d) { return twl_level_commit_from_dp(ctx.stores[d], finalPaths, finalLen.data(), lv.pathStride, lv.route.inPlace ? rows.fromDp.data() : nullptr); });
+#pragma omp parallel for schedule(static) if (lv.n >= 512)
+    for (int i = 0; i < lv.n; ++i) {            // Node bookkeeping of updateFrequency / updateAlignment (alignment-helper.cpp:474-478,536-538); the pairs of a level share no node
+        if (finalLen[i] == 0) continue;
+        Node *a = nodes[i].first, *b = nodes[i].second;
+        if (a->cacheId >= 0 && b->cacheId >= 0) b->cacheId = -1;       // merged into a's cache by the commit
+        a->alnNum += b->alnNum;
+        a->alnLen = finalLen[i];
+        a->alnWeight += b->alnWeight;
+        a->seqsIncluded.insert(a->seqsIncluded.end(), b->seqsIncluded.begin(), b->seqsIncluded.end());
+        b->seqsIncluded.clear();
+    }
+}
 
 }  // namespace
 
@@ -202,7 +629,7 @@ void alignmentKernel_Resident(Tree *T, NodePairVec &nodes, SequenceDB *database,
         alignmentKernel_GPU(T, nodes, database, option, param);
         return;
     }
-    if (option->cpuOnly) { std::cerr << "ERROR: --cpu-only is not available: this build has no CPU alignment path.\n"; exit(1); }
+    refuseCpuOnly(option);
     ensureInit(option);
     uploadSequences(database, option);
     if (ctx.shard.world > 1 && ctx.stores.size() > 1) { std::cerr << "ERROR: several processes with several device replicas each are not supported.\n"; exit(1); }
@@ -211,345 +638,44 @@ void alignmentKernel_Resident(Tree *T, NodePairVec &nodes, SequenceDB *database,
     rec.task = task;
     const LevelTotals before = ctx.totals;
     const double tPrep = nowMs();
-    const int n = (int)nodes.size();
-    static const char bases[] = {'A', 'C', 'G', 'T', 'N'};
-    static const char acids[] = {'A', 'C', 'D', 'E', 'F', 'G', 'H', 'I', 'K', 'L', 'M', 'N', 'P', 'Q', 'R', 'S', 'T', 'V', 'W', 'Y', 'X'};
-    const char *letters = (option->type == 'n') ? bases : acids;
-
-    // ---- side descriptors (what calculateProfile reads from the two nodes, alignment-helper.cpp:8-40) ----
-    std::vector<twl_side> sides(2 * (size_t)n);
-    std::vector<PairState> ps(n);
-    size_t nMembers = 0;
-    int stride = 1;
-    // (what is read from the nodes and sequences of a pair -- cache misses, mostly -- in parallel; the running member offsets and the
-    // ids of newly cached profiles, which depend on the order of the pairs, in a serial pass behind it)
-#pragma omp parallel for schedule(static) if (n >= 512)
-    for (int i = 0; i < n; ++i) {
-        Node *nd[2] = {nodes[i].first, nodes[i].second};
-        PairState &s = ps[i];
-        s.refLen = nd[0]->getAlnLen(0); s.qryLen = nd[1]->getAlnLen(0);
-        s.refNum = nd[0]->getAlnNum(0); s.qryNum = nd[1]->getAlnNum(0);
-        for (int sd = 0; sd < 2; ++sd) {
-            twl_side &x = sides[2 * (size_t)i + sd];
-            x.n_members = (int32_t)nd[sd]->seqsIncluded.size();
-            x.len = sd ? s.qryLen : s.refLen;
-            x.num = sd ? s.qryNum : s.refNum;
-            x.weight = nd[sd]->alnWeight;
-            x.cache_id = nd[sd]->cacheId;
-            x.store_id = -1;
-            x.reserved = 0;
-        }
-        s.lowQ_r = (option->alnMode == MERGE_MSA) ? false : ((s.refNum > 1) ? false : database->sequences[nd[0]->seqsIncluded[0]]->lowQuality);
-        s.lowQ_q = (option->alnMode == MERGE_MSA) ? false : ((s.qryNum > 1) ? false : database->sequences[nd[1]->seqsIncluded[0]]->lowQuality);
-    }
-    for (int i = 0; i < n; ++i) {
-        PairState &s = ps[i];
-        Node *nd[2] = {nodes[i].first, nodes[i].second};
-        const bool storeFreq = (s.refNum >= option->calProfileTh || s.qryNum >= option->calProfileTh) || (sides[2 * (size_t)i].cache_id >= 0 || sides[2 * (size_t)i + 1].cache_id >= 0);
-        for (int sd = 0; sd < 2; ++sd) {
-            twl_side &x = sides[2 * (size_t)i + sd];
-            x.member_off = (int32_t)nMembers;
-            if (storeFreq && x.cache_id < 0) x.store_id = nd[sd]->cacheId = ctx.nextCacheId++;
-            nMembers += (size_t)x.n_members;
-            stride = std::max(stride, x.len);
-        }
-    }
-    std::vector<int32_t> members(nMembers);
-    std::vector<float> weights(nMembers);
-    // (levels of a few pairs stay on this thread: a parallel region of one iteration wakes every worker, and their spinning at its end
-    // slowed the serial stretches that follow -- 1.3 ms against 0.3 ms for the 100 000 members of a top level)
-#pragma omp parallel for schedule(dynamic, 16) if (n >= 64)
-    for (int i = 0; i < n; ++i) {
-        Node *nd[2] = {nodes[i].first, nodes[i].second};
-        for (int sd = 0; sd < 2; ++sd) {
-            const twl_side &x = sides[2 * (size_t)i + sd];
-            const float groupWeight = nd[sd]->alnWeight;
-            for (int m = 0; m < x.n_members; ++m) {
-                const int sIdx = nd[sd]->seqsIncluded[m];
-                if (sIdx < 0) { std::cerr << "ERROR: compressed sequence group in device-resident mode.\n"; exit(1); }
-                members[x.member_off + m] = sIdx;
-                weights[x.member_off + m] = database->sequences[sIdx]->weight / groupWeight * x.num;     // alignment-helper.cpp:27
-            }
-        }
-    }
-
-    // ---- device: profiles, consensus, gappy-column removal, gap penalties ----
-    twl_params tp = baseParams(param);
-    std::vector<int32_t> lens(2 * (size_t)n);
-    const int nd = (int)ctx.stores.size();
-    std::vector<std::vector<int32_t>> lensOf(nd);
-    onAllStores(ctx, "twl_level_prepare", [&](int d) {
-        lensOf[d].resize(2 * (size_t)n);       // every replica prepares the whole level; column info is fetched from the first only, below
-        return twl_level_prepare(ctx.stores[d], &tp, option->gappyVertical, n, sides.data(), members.data(), weights.data(), stride,
-                                 d == 0 ? lens.data() : lensOf[d].data(), nullptr);
-    });
-    for (int d = 1; d < nd; ++d)
-        if (lensOf[d] != lens) { std::cerr << "ERROR: device replicas disagree on the prepared level.\n"; exit(1); }
-    const bool removal = !(option->gappyVertical == 1.0);
-    // The column info (consensus letter + gappy flag per original column) only matters for addGappyColumnsBack, i.e. for pairs in
-    // which some column was removed: fetch it for those (at the leaf level none: single sequences have no gap columns).
-    std::vector<int> needInfo;
-    for (int i = 0; i < n; ++i) {
-        PairState &s = ps[i];
-        s.lens = {lens[2 * i], lens[2 * i + 1]};
-        if (s.lens.first != s.refLen || s.lens.second != s.qryLen) needInfo.push_back(i);
-    }
-    // One device, one process: the paths never leave HBM -- pairs that lost no column commit their DP path as it is, the others get their
-    // columns back on the device (twl_level_restore); the column info comes to the host only for a pair the device hands back (below).
-    const bool procs = ctx.shard.world > 1;
-    // ... and so it is with several processes when they can all-gather device blocks (Shard::exchangeDev): each rank restores its own
-    // pairs on its device, the final paths travel HBM to HBM (exchangeFinalPaths below), every rank commits all of them from HBM.
-    const bool devX = (nd == 1 && (ctx.shard.exchangeDev != nullptr || ctx.shard.rccl));
-    const bool inPlace = (nd == 1 && ((!procs && !ctx.shard.exchange && !ctx.shard.rccl) || devX));
-    auto infoOf = [&](const std::vector<int> &which) {      // consensus + removed runs of these pairs, one synchronisation
-        uint8_t *info = reinterpret_cast<uint8_t *>(g_infoStage.get((size_t)2 * which.size() * stride));
-        const int rc = twl_level_read_colinfo_many(firstStore(ctx), (int32_t)which.size(), which.data(), info);
-        if (rc != TWL_OK) die("twl_level_read_colinfo_many", rc);
-#pragma omp parallel for schedule(dynamic, 4)
-        for (int t = 0; t < (int)which.size(); ++t) {
-            PairState &s = ps[which[t]];
-            runsAndConsensus(&info[((size_t)2 * t) * stride], s.refLen, removal, letters, s.gappy.first, s.consensus.first);
-            runsAndConsensus(&info[((size_t)2 * t + 1) * stride], s.qryLen, removal, letters, s.gappy.second, s.consensus.second);
-        }
-    };
-    if (inPlace) {}
-    else if (needInfo.size() * 8 > (size_t)n) {        // most pairs: one transfer of the level's block
-        uint8_t *info = reinterpret_cast<uint8_t *>(g_infoStage.get((size_t)2 * n * stride));
-        const int rc = twl_level_read_colinfo(firstStore(ctx), -1, 0, info);
-        if (rc != TWL_OK) die("twl_level_read_colinfo", rc);
-#pragma omp parallel for schedule(dynamic, 4)
-        for (int t = 0; t < (int)needInfo.size(); ++t) {
-            PairState &s = ps[needInfo[t]];
-            runsAndConsensus(&info[((size_t)2 * needInfo[t]) * stride], s.refLen, removal, letters, s.gappy.first, s.consensus.first);
-            runsAndConsensus(&info[((size_t)2 * needInfo[t] + 1) * stride], s.qryLen, removal, letters, s.gappy.second, s.consensus.second);
-        }
-    } else if (!needInfo.empty()) infoOf(needInfo);      // a few pairs: their blocks only
+    const int n = (int)nodes.size(), nd = (int)ctx.stores.size();
+    Level level(ctx, nodes, database, option, param);
+    describeLevel(level, ctx, nodes);
+    prepareOnReplicas(level, ctx);
+    const Level &lv = level;
+    PairRows rows(n);
+    // the column info comes to the host up front unless the paths stay in HBM: most pairs -> one transfer of the level's block; a few -> their blocks only
+    if (!lv.route.inPlace) fetchColumnInfo(lv, lv.needInfo, lv.needInfo.size() * 8 > (size_t)n, rows.cols);
     ctx.totals.prepare_ms += nowMs() - tPrep;
 
-    // ---- DP with the reference's grouping and retry/defer policy (alignment-cpu.cpp:88-130) ----
-    std::vector<alnPath> paths(n);
-    std::vector<int16_t> errs(n, 0);
-    std::vector<uint8_t> maskPlain(n, 0), maskZero(n, 0);
-    int nPlain = 0, nZero = 0;
-    for (int i = 0; i < n; ++i) {
-        if (ps[i].refLen == 0) paths[i].assign(ps[i].qryLen, 1);
-        if (ps[i].qryLen == 0) paths[i].insert(paths[i].end(), ps[i].refLen, 2);
-        if (!paths[i].empty() || ps[i].lowQ_r || ps[i].lowQ_q) continue;
-        const bool zg = (task == 1 || ps[i].refNum > 10000 || ps[i].qryNum > 10000);      // alignment-cpu.cpp:88
-        if (zg) { maskZero[i] = 1; ++nZero; } else { maskPlain[i] = 1; ++nPlain; }
-    }
-    // deal the pairs, longest first (cost ~ R + Q after gappy-column removal), to the device replicas of this process or, with several
-    // processes (one device each), to the ranks; everybody aligns its share
-    std::vector<char> takesPart(n, 0);
-    std::vector<long long> cost(n, 0);
-    for (int i = 0; i < n; ++i) { takesPart[i] = (maskPlain[i] || maskZero[i]) ? 1 : 0; cost[i] = (long long)ps[i].lens.first + ps[i].lens.second; }
-    const std::vector<int> owner = dealPairs(cost, takesPart, procs ? ctx.shard.world : nd);
-    const int meBase = procs ? ctx.shard.rank : 0;       // replica d of this process aligns the pairs of owner meBase + d
-    twl_params tz = tp;
-    tz.gap_char = 0;
+    planDp(level, rows);
+    std::vector<ReplicaShare> shares(nd);
     if (g_alnStage.size() < (size_t)nd) g_alnStage.resize((size_t)nd);
-    std::vector<double> callMs(nd, 0), kernMs(nd, 0), totMs(nd, 0);
-    std::vector<uint64_t> cellsOf(nd, 0), redoOf(nd, 0);
-    std::vector<char> needsHost(n, 0);
-    for (int i : needInfo) needsHost[i] = 1;
-    std::vector<int> handedBack;             // in-place mode: pairs the device handed back to the host (twl_level_restore returned -1)
-    std::vector<uint8_t> fromDp(n, 0);       // 1: the DP path is the final path; 2: twl_level_restore made the final path, in HBM
-    std::vector<int32_t> dpLen(n, 0);
-    int pathStride = 1;                      // row pitch of the final paths: refLen + qryLen before removal bounds every path
-    for (int i = 0; i < n; ++i) pathStride = std::max(pathStride, ps[i].refLen + ps[i].qryLen);
-    onAllStores(ctx, "twl_level_align", [&](int d) {
-        int8_t *aln = inPlace ? nullptr : reinterpret_cast<int8_t *>(g_alnStage[d].get((size_t)n * 2 * stride));
-        std::vector<int32_t> alnLen(n);
-        std::vector<int16_t> err(n);
-        {
-            // ONE launch for the pairs of both gap-character kinds (alignment-cpu.cpp:88 decides per pair; until round 4 one call per kind, which
-            // doubled the latency of the top levels of a 100 000-leaf tree, where a few pairs of each kind meet)
-            std::vector<uint8_t> mask(n, 0);
-            int cnt = 0, cntZero = 0;
-            for (int i = 0; i < n; ++i) if ((maskPlain[i] || maskZero[i]) && owner[i] == meBase + d) { mask[i] = 1; ++cnt; cntZero += maskZero[i]; }
-            if (!cnt) return (int)TWL_OK;
-            const double tCall = nowMs();
-            const int r = (cntZero == cnt) ? twl_level_align(ctx.stores[d], &tz, mask.data(), aln, alnLen.data(), err.data())
-                                           : twl_level_align_mixed(ctx.stores[d], &tp, mask.data(), cntZero ? maskZero.data() : nullptr, aln, alnLen.data(), err.data());
-            if (r != TWL_OK) return r;
-            callMs[d] += nowMs() - tCall;
-            auto addStats = [&]() {
-                twl_stats st{};
-                if (nd == 1 || ctx.storeDev[d] != ctx.storeDev[(d + 1) % nd]) {      // per-device counters (virtual replicas share one device: see below)
-                    if (twl_get_stats(ctx.storeDev[d], &st) == TWL_OK) { cellsOf[d] += st.band_cells; redoOf[d] += (uint64_t)st.n_relaunched; kernMs[d] += st.kernel_ms; totMs[d] += st.total_ms; if (d == 0 && rec.matrix_mode < 0) { rec.matrix_mode = st.matrix_mode; rec.speculative = st.speculative; memcpy(rec.kernel, st.kernel, sizeof rec.kernel); } if (d == 0) { rec.mt_predicted += st.mt_tiles_predicted; rec.mt_inline += st.mt_tiles_inline; } }
-                }
-            };
-            addStats();
-            if (d == 0) { twl_stats st0{}; if (twl_get_stats(ctx.storeDev[0], &st0) == TWL_OK) ctx.totals.nominal_cells += st0.nominal_cells; }      // (R*Q of the level's pairs, once: the classic GCUPS figure of bench.py)
-            // alignment-cpu.cpp:116-129: in the deferred pass a failed pair is retried, by whoever owns it, with a larger X-drop / band limit until it passes
-            if (task == 1) {
-                // a retry is a call of the whole level with a one-pair mask, and a DP call zero-fills the outputs of ALL the level's pairs: with more
-                // than one pair it would wipe what the others have just produced.  The deferred pass aligns one profile per level
-                // (progressive.cpp:283-291); a task-1 level of several pairs is refused up front -- whether or not a pair fails -- rather than silently
-                // wrong or dependent on the data (the limit is part of the contract: include/twl_msa.h)
-                if (n != 1) { std::cerr << "ERROR: a deferred-pass (task 1) level must hold exactly one pair; this one has " << n << ".\n"; return (int)TWL_ERR_UNSUPPORTED; }
-                for (int i = 0; i < n; ++i) {
-                    if (!mask[i] || err[i] == 0) continue;
-                    twl_params tr = maskZero[i] ? tz : tp;
-                    const int minLen = std::min(ps[i].lens.first, ps[i].lens.second);
-                    std::vector<uint8_t> one(n, 0);
-                    one[i] = 1;
-                    std::vector<int32_t> len1(n);
-                    std::vector<int16_t> err1(n);
-                    while (err[i] != 0) {
-                        nextRetryParams(err[i], minLen, tr);
-                        if (option->printDetail) std::cout << "Retry pair No. " << i << "\txdrop " << tr.xdrop << " flen " << tr.flen << '\n';
-                        const double tRetry = nowMs();
-                        const int rr = twl_level_align(ctx.stores[d], &tr, one.data(), aln, len1.data(), err1.data());
-                        if (rr != TWL_OK) return rr;
-                        callMs[d] += nowMs() - tRetry;
-                        addStats();
-                        err[i] = err1[i]; alnLen[i] = len1[i];
-                    }
-                }
-            }
-            std::vector<int32_t> fetch, fetchLen, restore, restoreLen;
-            for (int i = 0; i < n; ++i) {
-                if (!mask[i]) continue;
-                errs[i] = err[i];
-                const int32_t len = (err[i] == 0) ? alnLen[i] : 0;
-                if (!inPlace) paths[i].assign(&aln[(size_t)i * 2 * stride], &aln[(size_t)i * 2 * stride] + len);
-                else if (needsHost[i]) {
-                    const bool lowQ = task == 0 && (ps[i].refNum == 1 || ps[i].qryNum == 1) && (ps[i].lowQ_r || ps[i].lowQ_q);      // (deferred below: its path is dropped)
-                    if (len > 0 && !lowQ) { restore.push_back(i); restoreLen.push_back(len); } else paths[i].clear();
-                }
-                else if (len > 0) { fromDp[i] = 1; dpLen[i] = len; }
-            }
-            if (!restore.empty()) {             // gappy columns back on the device: these paths never leave HBM either
-                std::vector<int32_t> fin(restore.size(), -1);
-                const int r3 = twl_level_restore(ctx.stores[d], &tp, (int32_t)restore.size(), restore.data(), pathStride, fin.data());
-                if (r3 != TWL_OK) return r3;
-                for (size_t t = 0; t < restore.size(); ++t) {
-                    if (fin[t] > 0) { fromDp[restore[t]] = 2; dpLen[restore[t]] = fin[t]; }
-                    else { fetch.push_back(restore[t]); fetchLen.push_back(restoreLen[t]); }      // a two-sided run too large for the device: on the host, as before
-                }
-            }
-            if (!fetch.empty()) {               // the pairs the host has to edit: their column info and paths only
-                infoOf(std::vector<int>(fetch.begin(), fetch.end()));
-                handedBack.insert(handedBack.end(), fetch.begin(), fetch.end());
-                int8_t *blk = reinterpret_cast<int8_t *>(g_alnStage[d].get(fetch.size() * (size_t)2 * stride));
-                const int r2 = twl_level_read_paths(ctx.stores[d], (int32_t)fetch.size(), fetch.data(), fetchLen.data(), blk, 2 * stride);
-                if (r2 != TWL_OK) return r2;
-                for (size_t t = 0; t < fetch.size(); ++t) paths[fetch[t]].assign(&blk[t * (size_t)2 * stride], &blk[t * (size_t)2 * stride] + fetchLen[t]);
-            }
-        }
-        return (int)TWL_OK;
-    });
-    (void)nPlain; (void)nZero;
-#ifdef TWL_DEV      // development builds: one line per pair for tools/sim_schedule.py
-    if (const char *dump = getenv("TWL_DUMP_SCHEDULE")) {
-        if (FILE *f = fopen(dump, "a")) {
-            std::vector<uint64_t> pc(n, 0);
-            if (nd == 1) (void)twl_get_pair_cells(ctx.storeDev[0], pc.data(), n);
-            for (int i = 0; i < n; ++i)
-                fprintf(f, "%d %d %d %d %d %d %d %llu\n", (int)ctx.levels.size(), i, nodes[i].first->seqsIncluded.empty() ? -1 : nodes[i].first->seqsIncluded[0],
-                        nodes[i].second->seqsIncluded.empty() ? -1 : nodes[i].second->seqsIncluded[0], ps[i].lens.first, ps[i].lens.second, (int)errs[i], (unsigned long long)pc[i]);
-            fclose(f);
-        }
-    }
+    onAllStores(ctx, "twl_level_align", [&](int d) { return alignShare(lv, d, rows, shares[d]); });
+#ifdef TWL_DEV
+    dumpSchedule(lv, rows);
 #endif
-    ctx.totals.call_ms += *std::max_element(callMs.begin(), callMs.end());           // the replicas run concurrently
-    ctx.totals.total_ms += *std::max_element(totMs.begin(), totMs.end());
-    rec.kernel_ms = *std::max_element(kernMs.begin(), kernMs.end());
-    for (uint64_t c : cellsOf) rec.band_cells += c;
-    for (uint64_t c : redoOf) rec.relaunched += c;
-    // gappy columns back on the host for one pair (alignment-helper.cpp:324-375)
-    auto restoreOnHost = [&](int i, alnPath &full) {
-        PairState &s = ps[i];
-        int alnRef = 0, alnQry = 0;
-        for (auto a : paths[i]) { if (a != 1) ++alnRef; if (a != 2) ++alnQry; }
-        alignment_helper::addGappyColumnsBack(paths[i], full, s.gappy, param, {alnRef, alnQry}, s.consensus);
-        alnRef = alnQry = 0;
-        for (auto a : full) { if (a != 1) ++alnRef; if (a != 2) ++alnQry; }
-        if (alnRef != s.refLen) std::cout << "R: Post " << nodes[i].first->identifier << "(" << alnRef << "/" << s.refLen << ")\n";
-        if (alnQry != s.qryLen) std::cout << "Q: Post " << nodes[i].second->identifier << "(" << alnQry << "/" << s.qryLen << ")\n";
-        if ((int)full.size() > pathStride) { std::cerr << "ERROR: path longer than both profiles together.\n"; exit(1); }
-    };
-    for (int i : handedBack) {                // (rare: a two-sided run too large for the device) the host's result joins the others in HBM
-        if (errs[i] != 0 || paths[i].empty()) continue;
-        alnPath full;
-        restoreOnHost(i, full);
-        const int rc = twl_level_write_final(firstStore(ctx), i, full.data(), (int32_t)full.size());
-        if (rc != TWL_OK) die("twl_level_write_final", rc);
-        fromDp[i] = 2; dpLen[i] = (int32_t)full.size();
-        paths[i].clear();
-    }
-    if (devX) {                               // HBM to HBM
-        std::vector<int32_t> bound(n);
-        for (int i = 0; i < n; ++i) bound[i] = ps[i].refLen + ps[i].qryLen;
-        exchangeFinalPaths(ctx, firstStore(ctx), ctx.storeDev[0], tp, owner, takesPart, bound, pathStride, fromDp, dpLen, errs, rec);
-    }
-    else exchangePaths(ctx, owner, takesPart, 2 * stride, paths, errs, rec);             // several processes: everybody gets every path
-    std::vector<int> fallbackPairs;
-    for (int i = 0; i < n; ++i) {
-        if (errs[i] == 0) continue;
-        if (errs[i] == 3 || task != 0) { std::cout << "There might be some bugs in the code!\n"; exit(1); }      // (the deferred pass retried until errorType 0)
-        paths[i].clear();                       // currentTask == 0: a failed pair is deferred (alignment-cpu.cpp:108-115)
-        fromDp[i] = 0;
-        fallbackPairs.push_back(i);
-    }
+    mergeShares(shares, ctx, rec);
+    joinHandedBack(lv, shares[0], rows);
+    exchange(lv, ctx, rows, rec);
+    std::vector<int> fallbackPairs = judgeFailures(lv, rows);
 
-    // ---- gappy columns back, then the write-back on the device ----
     const double tFin = nowMs();
-    int8_t *finalPaths = reinterpret_cast<int8_t *>(g_finalStage.get((size_t)n * pathStride));
     std::vector<int32_t> finalLen(n, 0);
     std::vector<char> deferred(n, 0);
-    std::vector<int> onHost;                 // pairs whose final path the host still has to make (none in the in-place mode: their paths are in HBM)
-    for (int i = 0; i < n; ++i) {
-        PairState &s = ps[i];
-        deferred[i] = (task == 0 && (s.refNum == 1 || s.qryNum == 1) && (s.lowQ_r || s.lowQ_q)) ? 1 : 0;          // :136-144
-        if (deferred[i]) { paths[i].clear(); fromDp[i] = 0; }
-        if (fromDp[i]) { finalLen[i] = dpLen[i]; continue; }      // no column was removed: the DP path is the final path, and it is in HBM
-        if (!paths[i].empty()) onHost.push_back(i);
-    }
-#pragma omp parallel for schedule(dynamic, 1) if (onHost.size() > 1)
-    for (int t = 0; t < (int)onHost.size(); ++t) {
-        const int i = onHost[t];
-        PairState &s = ps[i];
-        if (s.gappy.first.empty() && s.gappy.second.empty()) {      // nothing was removed: the DP path is the final path (addGappyColumnsBack would copy it)
-            if ((int)paths[i].size() > pathStride) { std::cerr << "ERROR: path longer than both profiles together.\n"; exit(1); }
-            std::copy(paths[i].begin(), paths[i].end(), &finalPaths[(size_t)i * pathStride]);
-            finalLen[i] = (int32_t)paths[i].size();
-            continue;
-        }
-        alnPath full;
-        restoreOnHost(i, full);
-        std::copy(full.begin(), full.end(), &finalPaths[(size_t)i * pathStride]);
-        finalLen[i] = (int32_t)full.size();
-    }
+    const int8_t *finalPaths = finalPathsOnHost(lv, rows, finalLen, deferred);
     const double tGappy = nowMs() - tFin;
-    onAllStores(ctx, "twl_level_commit", [&](int d) { return twl_level_commit_from_dp(ctx.stores[d], finalPaths, finalLen.data(), pathStride, inPlace ? fromDp.data() : nullptr); });
-#pragma omp parallel for schedule(static) if (n >= 512)
-    for (int i = 0; i < n; ++i) {               // Node bookkeeping of updateFrequency / updateAlignment (alignment-helper.cpp:474-478,536-538); the pairs of a level share no node
-        if (finalLen[i] == 0) continue;
-        Node *a = nodes[i].first, *b = nodes[i].second;
-        if (a->cacheId >= 0 && b->cacheId >= 0) b->cacheId = -1;       // merged into a's cache by the commit
-        a->alnNum += b->alnNum;
-        a->alnLen = finalLen[i];
-        a->alnWeight += b->alnWeight;
-        a->seqsIncluded.insert(a->seqsIncluded.end(), b->seqsIncluded.begin(), b->seqsIncluded.end());
-        b->seqsIncluded.clear();
-    }
+    commitAndBookkeep(lv, ctx, nodes, finalPaths, finalLen, rows);
     ctx.totals.finish_ms += nowMs() - tFin;
     double devPrep = 0, devCommit = 0;
     if (option->printDetail) twl_level_timing(firstStore(ctx), &devPrep, &devCommit);      // (waits for the write-back kernels, which the next level would otherwise overlap with)
     ctx.totals.dev_prepare_ms += devPrep;
     ctx.totals.dev_commit_ms += devCommit;
-    for (int i = 0; i < n; ++i)
-        if (deferred[i]) fallbackPairs.push_back(i);
-    if (!fallbackPairs.empty()) alignment_helper::fallback2cpu(fallbackPairs, nodes, database, option);
-    rec.level_ms = nowMs() - tPrep;
-    ctx.totals.pairs += (uint64_t)n; ctx.totals.band_cells += rec.band_cells; ctx.totals.relaunched += rec.relaunched; ctx.totals.kernel_ms += rec.kernel_ms; ctx.totals.exchange_ms += rec.exchange_ms;
-    ctx.levels.push_back(rec);
+    closeLevel(ctx, rec, tPrep, deferred, fallbackPairs, nodes, database, option);
     if (option->printDetail)
         std::cerr << "  phases (ms): prepare " << ctx.totals.prepare_ms - before.prepare_ms << " (device " << devPrep << ") call " << ctx.totals.call_ms - before.call_ms
                   << " (kernel " << rec.kernel_ms << ", exchange " << rec.exchange_ms << ") finish " << ctx.totals.finish_ms - before.finish_ms << " (device " << devCommit
-                  << ") whole " << nowMs() - tPrep << "; relaunched pairs " << ctx.totals.relaunched - before.relaunched << "; pairs with removed columns " << needInfo.size() << "; restored on the host " << handedBack.size() << "; gappy columns back " << tGappy << " ms\n";
+                  << ") whole " << nowMs() - tPrep << "; relaunched pairs " << ctx.totals.relaunched - before.relaunched << "; pairs with removed columns " << lv.needInfo.size() << "; restored on the host " << shares[0].handedBack.size() << "; gappy columns back " << tGappy << " ms\n";
 }
 
 }  // namespace gpu

@@ -463,14 +463,14 @@ void preparePair(NodePair &nodes, SequenceDB *database, Option *option, Params &
     alignment_helper::getConsensus(option, in.freq.data() + (size_t)P * in.memLen, in.consensus.second, in.qryLen);
     alignment_helper::removeGappyColumns(in.freq.data(), nodes, option, in.gappyColumns, in.memLen, in.lens, database->currentTask);
     alignment_helper::calculatePSGP(in.freq.data(), in.gapOp.data(), in.gapEx.data(), nodes, database, option, in.memLen, {0, 0}, in.lens, param);
-    in.lowQ_r = (option->alnMode == MERGE_MSA) ? false : ((in.refNum > 1) ? false : database->sequences[nodes.first->seqsIncluded[0]]->lowQuality);
-    in.lowQ_q = (option->alnMode == MERGE_MSA) ? false : ((in.qryNum > 1) ? false : database->sequences[nodes.second->seqsIncluded[0]]->lowQuality);
+    in.lowQ_r = lowQualitySide(option->alnMode == MERGE_MSA, in.refNum, firstSeqLowQuality(nodes.first, database));
+    in.lowQ_q = lowQualitySide(option->alnMode == MERGE_MSA, in.qryNum, firstSeqLowQuality(nodes.second, database));
 }
 
 // alignment-cpu.cpp:136-175: low-quality rule, gappy columns back, write-back.  aln_wo_gc empty = the DP produced no path.
 bool finishPair(NodePair &nodes, SequenceDB *database, Option *option, Params &param, PairInputs &in, alnPath &aln_wo_gc)
 {
-    if (database->currentTask == 0 && (in.refNum == 1 || in.qryNum == 1) && (in.lowQ_r || in.lowQ_q)) aln_wo_gc.clear();
+    if (deferredLowQuality(database->currentTask, in)) aln_wo_gc.clear();
     if (aln_wo_gc.empty()) return false;
     alnPath aln_w_gc;
     int alnRef = 0, alnQry = 0;

@@ -25,17 +25,11 @@
 namespace msa {
 
 using progressive::gpu::baseParams;
-using progressive::gpu::nextRetryParams;
+using progressive::gpu::die;
 using progressive::gpu::nowMs;
 using progressive::gpu::runsAndConsensus;
 
 namespace {
-
-[[noreturn]] void die(const char *what, int rc)
-{
-    std::cerr << "ERROR: " << what << " failed (" << rc << "): " << twl_last_error() << '\n';
-    exit(1);
-}
 
 // Device memory one pair of a chunk takes in the level buffers: raw profiles and packed DP columns of both sides (2 * seq_len * (2P + 2)
 // floats), the DP output and the column info.  A chunk gets kChunkBudget of it.
@@ -156,14 +150,13 @@ int runPlacement(Option &option)
             // a pair that failed in its chunk (alignment-cpu.cpp:95-128 with currentTask != 0): alone, retried until errorType 0
             twl_params tr = prm;
             const int32_t minLen = std::min(lenOut[0], lenOut[1]);
-            err[0] = (*errIn)[0];
-            while (err[0] != 0) {
-                nextRetryParams(err[0], minLen, tr);
+            progressive::retryUntilPassed(tr, (*errIn)[0], minLen, [&](const twl_params &grown) {
                 ++tot.retries;
-                if (option.printDetail) std::cout << "Retry sequence " << placed[ids[0] - B]->name << "\txdrop " << tr.xdrop << " flen " << tr.flen << '\n';
-                if ((rc = twl_level_align(st, &tr, nullptr, nullptr, alnLen.data(), err.data())) != TWL_OK) die("twl_level_align", rc);
+                if (option.printDetail) std::cout << "Retry sequence " << placed[ids[0] - B]->name << "\txdrop " << grown.xdrop << " flen " << grown.flen << '\n';
+                if ((rc = twl_level_align(st, &grown, nullptr, nullptr, alnLen.data(), err.data())) != TWL_OK) die("twl_level_align", rc);
                 if (twl_get_stats(device, &ss) == TWL_OK) { tot.cells += ss.band_cells; tot.kernel += ss.kernel_ms; }
-            }
+                return err[0];
+            });
         }
         tot.dp += nowMs() - t0;
         // gappy columns back (alignment-helper.cpp:324-375) for the pairs that lost a column; the others are final as the DP left them

@@ -6,6 +6,7 @@
 // is injected exactly where the reference injects cpu::alignmentKernel_CPU (twilight-main.cpp:148).
 // No Boost, no TBB: options are a plain struct, parallel loops are OpenMP.
 #pragma once
+#include "level_policy.hpp"
 
 #include <cstdint>
 #include <cstdlib>
@@ -236,14 +237,18 @@ struct FloatBuf {
     void assign(size_t n, float v) { ext = nullptr; own.assign(n, v); }
     void bind(float *slot, size_t n) { ext = slot; std::fill(slot, slot + n, 0.0f); }
 };
-struct PairInputs {
+struct PairInputs : PairShape {                      // (level_policy.hpp: lengths, sequence counts, low-quality flags)
     FloatBuf freq, gapOp, gapEx;                     // freq[2][memLen][P], gapOp/gapEx[2][memLen]
     std::pair<IntPairVec, IntPairVec> gappyColumns;
     stringPair consensus;
-    IntPair lens;                                    // after gappy-column removal
-    int32_t refLen, qryLen, refNum, qryNum, memLen;
-    bool lowQ_r, lowQ_q;
+    int32_t memLen;
 };
+// the lowQuality flag of a side's first sequence, for lowQualitySide (a side of several sequences may start with a compressed group: no flag)
+inline bool firstSeqLowQuality(const Node *node, const SequenceDB *database)
+{
+    const int s = node->seqsIncluded.empty() ? -1 : node->seqsIncluded[0];
+    return s >= 0 && s < (int)database->sequences.size() && database->sequences[s]->lowQuality;
+}
 // With slots given, the pair's buffers are built in place there with row stride `stride` (>= max(refLen, qryLen)); the stride
 // is only an address stride (alignment-cpu.cpp:13-30 uses max(refLen, qryLen)), it does not enter any value.
 void preparePair(NodePair &nodes, SequenceDB *database, Option *option, Params &param, PairInputs &in, float *freqSlot = nullptr,
@@ -255,8 +260,8 @@ namespace gpu {
 void alignmentKernel_GPU(Tree *T, NodePairVec &alnPairs, SequenceDB *database, Option *option, Params &param);
 void beginInit(Option *option);   // optional: start device initialisation early, on a helper thread
 // Device-resident variant (include/twl_level.h): rows and cached profiles stay in HBM during the main progressive pass; profile
-// building, gappy-column removal, gap penalties and the row write-back run as kernels.  Falls through to alignmentKernel_GPU
-// for the deferred pass (currentTask != 0), after bringing the rows back.
+// building, gappy-column removal, gap penalties and the row write-back run as kernels.  The deferred pass (currentTask 1) runs on
+// the resident rows too; currentTask 2, or a run whose rows are back on the host, falls through to alignmentKernel_GPU.
 void alignmentKernel_Resident(Tree *T, NodePairVec &alnPairs, SequenceDB *database, Option *option, Params &param);
 struct LevelTotals { uint64_t band_cells = 0, pairs = 0, relaunched = 0, nominal_cells = 0 /* sum of R*Q over the pairs this process's level calls saw (all of them on one GPU) */; double kernel_ms = 0, total_ms = 0, prepare_ms = 0, stage_ms = 0, call_ms = 0, finish_ms = 0, dev_prepare_ms = 0, dev_commit_ms = 0, exchange_ms = 0; };
 // One level-kernel call, as the reference's per-level report line (progressive.cpp:178-189) plus what the DP did in it.

@@ -136,3 +136,193 @@ def expected(case: PairCase, path_wo_gc: Optional[np.ndarray] = None) -> dict:
     c0, c1 = out["cache_after_prepare"]
     out["merged"] = LO.update_frequency(c0, c1, full, case.sides[0].group_weight, case.sides[1].group_weight) if (c0 is not None and c1 is not None) else None
     return out
+
+
+# ---- directed cases: the shapes at which the level and restore kernels switch scans, chunks and scratch tiers ----
+
+def _pair_of(x):
+    return (x, x) if np.isscalar(x) else tuple(x)
+
+
+def make_edge_case(seq_type: str, seed: int, *, members=(1, 1), length=80, lead=(0, 0), trail=(0, 0), runs=((), ()), thr: float = 0.95,
+                   identical: bool = False, cached: int = 0) -> PairCase:
+    """A pair whose removed runs are placed by the caller.
+
+    length   kept columns per side (int or pair); a side's rows are lead + length + sum(run lengths) + trail columns long
+    lead / trail   all-gap columns in front of / behind the kept columns, per side: (0, 40) is a one-sided lead, (31, 127) a two-sided one
+    runs     per side a list of (position, run length): an all-gap run in front of kept column `position` (0 < position < length)
+    identical   both sides are ONE member with the same kept letters and no other gap: the DP path is `length` matches, so leads meet at
+                boundary 0, trails at boundary `length`, and runs at the same position on both sides at that boundary
+    Otherwise member 0 of a side has a letter in every kept column, the others gaps in 8 % of them (columns that the weights push over
+    `thr` are removed as well: ask classify() what a case holds).  cached as in make_case."""
+    rng = np.random.default_rng(7919 * seed + (3 if seq_type == "n" else 5))
+    case = PairCase(seq_type=seq_type, thr=thr, seed=seed)
+    alpha = np.frombuffer(("ACGT" if seq_type == "n" else LO.AA).encode(), dtype=np.uint8)
+    odd = np.frombuffer(("NRY" if seq_type == "n" else "XBZ").encode(), dtype=np.uint8)
+    kept_len, members = _pair_of(length), _pair_of(members)
+    if identical:
+        assert members == (1, 1) and kept_len[0] == kept_len[1]
+        shared = alpha[rng.integers(0, len(alpha), size=kept_len[0])]
+    for sd in range(2):
+        k, n = members[sd], kept_len[sd]
+        if identical:
+            kept = shared[None, :].copy()
+        else:
+            base = alpha[rng.integers(0, len(alpha), size=n)]
+            kept = np.repeat(base[None, :], k, axis=0)
+            mut = rng.random((k, n)) < 0.15
+            kept[mut] = alpha[rng.integers(0, len(alpha), size=int(mut.sum()))]
+            amb = rng.random((k, n)) < 0.02
+            kept[amb] = odd[rng.integers(0, len(odd), size=int(amb.sum()))]
+            low = rng.random((k, n)) < 0.1
+            kept[low] |= 0x20
+            gaps = rng.random((k, n)) < 0.08
+            gaps[0] = False
+            kept[gaps] = ord("-")
+        ins = np.zeros(n + 1, dtype=np.int64)              # all-gap columns in front of kept column j (j == n: behind the last one)
+        ins[0], ins[n] = lead[sd], ins[n] + trail[sd]
+        if n == 0:
+            ins[0] = lead[sd] + trail[sd]
+        for pos, ln in runs[sd]:
+            assert 0 < pos < n
+            ins[pos] += ln
+        where = np.arange(n) + np.cumsum(ins[:n])           # original index of every kept column
+        L = n + int(ins.sum())
+        mat = np.full((k, L), ord("-"), dtype=np.uint8)
+        mat[:, where] = kept
+        rows = [mat[m].tobytes() for m in range(k)]
+        w = rng.uniform(0.5, 2.0, size=k).astype(F)
+        gw = F(0)
+        for x in w:
+            gw = F(gw + x)
+        side = SideCase(rows=rows, seq_weights=w, group_weight=float(gw))
+        if cached == 2 or (cached == 1 and sd == 0):
+            prof = LO.calculate_profile(rows, LO.member_weights(w, gw, k), case.P, seq_type)
+            side.cache = LO.cache_from_profile(prof, gw, k)
+        case.sides.append(side)
+    return case
+
+
+# constants of restore_kernels.hip.h / level_kernels.hip.h that classify() speaks about
+NW_SMALL, NW_CELLS, NW_ROW, SEG_DIRECT = 31, 4096, 128, 32
+RUNS_ROUND, INDEX_ROUND, WRITE_CHUNK, SCAN_ROUND = 1024 * 8, 1024 * 16, 1024, 65536
+
+
+def boundaries(path, runs_r, runs_q):
+    """(boundary, run length ref, run length query) for every boundary of `path` (0 .. len(path)) at which addGappyColumnsBack
+    (alignment-helper.cpp:324-375) inserts a removed run: the walk of LO.add_gappy_columns_back without the small alignments."""
+    out, r, q, gr, gq = [], 0, 0, 0, 0
+    for a in range(len(path) + 1):
+        lr = runs_r[gr][1] if gr < len(runs_r) and r == runs_r[gr][0] else 0
+        lq = runs_q[gq][1] if gq < len(runs_q) and q == runs_q[gq][0] else 0
+        if lr or lq:
+            out.append((a, lr, lq))
+            gr += 1 if lr else 0
+            gq += 1 if lq else 0
+            r += lr
+            q += lq
+        if a < len(path):
+            c = int(path[a])
+            r += c != 1
+            q += c != 2
+    return out
+
+
+def too_big(lr, lq):
+    """restore_runs_kernel hands a pair back for a two-sided boundary whose traceback or row does not fit one thread's scratch."""
+    return lr > 0 and lq > 0 and ((lr + 1) * (lq + 1) > NW_CELLS or lq + 1 > NW_ROW)
+
+
+def classify(case: PairCase, path_wo_gc, exp: Optional[dict] = None) -> dict:
+    """Which branches of the restore and write-back kernels the pair reaches with DP path `path_wo_gc`, from the checker's own runs.
+    Returns the measured facts and, under "tiers", the set of names of the branches."""
+    exp = exp if exp is not None else expected(case, path_wo_gc=np.asarray(path_wo_gc, dtype=np.int8))
+    n = len(path_wo_gc)
+    bs = boundaries(path_wo_gc, exp["runs"][0], exp["runs"][1])
+    both = [(a, lr, lq) for a, lr, lq in bs if lr and lq]
+    one = [(a, lr, lq) for a, lr, lq in bs if not (lr and lq)]
+    fits = [(a, lr, lq) for a, lr, lq in both if not too_big(lr, lq)]
+    lens_orig = tuple(len(s.rows[0]) for s in case.sides)
+    tiers = set()
+    if any(max(lr, lq) <= NW_SMALL for _, lr, lq in fits): tiers.add("nw_lds")
+    if any(max(lr, lq) > NW_SMALL for _, lr, lq in fits): tiers.add("nw_global")
+    if len(fits) < len(both): tiers.add("hand_back")
+    if any(max(lr, lq) > SEG_DIRECT for _, lr, lq in one): tiers.add("queued_one_sided")
+    if any(max(lr, lq) > SEG_DIRECT for _, lr, lq in fits): tiers.add("queued_two_sided")      # (the small alignment is at least as long as its longer run)
+    if any(a == n for a, _, _ in bs): tiers.add("trailing_run")
+    if any(a == n for a, _, _ in both): tiers.add("trailing_two_sided")
+    if any(a == 0 for a, _, _ in one): tiers.add("lead_one_sided")
+    if any(a == 0 for a, _, _ in both): tiers.add("lead_two_sided")
+    if n + 1 > RUNS_ROUND: tiers.add("runs_rounds")
+    if max(lens_orig) > INDEX_ROUND: tiers.add("index_rounds")
+    if n + 1 > WRITE_CHUNK: tiers.add("write_chunks")
+    if len(exp["path_full"]) > SCAN_ROUND: tiers.add("scan_rounds")
+    return {"n": n, "final_len": len(exp["path_full"]), "boundaries": bs, "both": both, "largest_both": max(both, key=lambda t: (t[1] + 1) * (t[2] + 1), default=None),
+            "arena": sum(lr + lq for _, lr, lq in both), "lens_orig": lens_orig, "lens": exp["lens"], "tiers": tiers}
+
+
+# ---- the restore cases of tests/test_gpu_level_edges.py, with the branch each exists for (tests/test_level_edge_inputs_cpu.py holds them to it
+# on the DP oracle's path, the GPU tests on the device's own path) ----
+
+@dataclass
+class EdgeSpec:
+    name: str
+    case: PairCase
+    need: frozenset                      # tiers classify() must report
+    n: Optional[int] = None              # exact length of the DP path
+    largest: Optional[tuple] = None      # (run ref, run query) of the largest two-sided boundary
+    hand_back: bool = False              # the device must report -1 for this pair (and for no other)
+
+
+def sprinkled(n: int):
+    """Short runs all along `n` kept columns: every 97th position on the reference side, every second of those also on the query side
+    (a two-sided boundary), and query-only runs in between."""
+    r = {int(p): 1 + (k % 3) for k, p in enumerate(range(37, n - 1, 97))}
+    q = {int(p): 1 + (k % 2) for k, p in enumerate(range(37, n - 1, 194))}
+    for p in range(80, n - 1, 211):
+        q.setdefault(int(p), 2)
+    return (sorted(r.items()), sorted(q.items()))
+
+
+def check_spec(spec: EdgeSpec, cl: dict):
+    """The case reaches what it exists for: raises AssertionError otherwise."""
+    assert spec.need <= cl["tiers"], f"{spec.name}: needs {sorted(spec.need - cl['tiers'])}, reaches {sorted(cl['tiers'])}"
+    assert spec.n is None or cl["n"] == spec.n, f"{spec.name}: DP path of {cl['n']} elements, not {spec.n}"
+    assert spec.largest is None or (cl["largest_both"] is not None and cl["largest_both"][1:] == spec.largest), f"{spec.name}: largest two-sided boundary {cl['largest_both']}"
+    assert spec.hand_back == ("hand_back" in cl["tiers"]), f"{spec.name}: hand_back {'hand_back' in cl['tiers']}"
+
+
+def restore_specs(seq_type: str, group: str) -> List[EdgeSpec]:
+    E = make_edge_case
+    out: List[EdgeSpec] = []
+
+    def add(name, need, n=None, largest=None, hand_back=False, **kw):
+        out.append(EdgeSpec(name, E(seq_type, 500 + len(out), **kw), frozenset(need), n, largest, hand_back))
+
+    if group == "scan":            # rounds of the three scans and chunks of the write pass; runs throughout, so every round's carried base matters
+        for n in (1023, 1024, 1025, 8191, 8192, 8193, 20000):
+            need = {"nw_lds", "trailing_run"} | ({"write_chunks"} if n + 1 > WRITE_CHUNK else set()) | ({"runs_rounds"} if n + 1 > RUNS_ROUND else set()) | \
+                   ({"index_rounds"} if n > INDEX_ROUND else set())
+            add(f"ident{n}", need, n=n, length=n, identical=True, runs=sprinkled(n), trail=(1 + n % 3, (n + 1) % 2), lead=(n % 2, 0))
+    elif group == "runs":          # leads and trails, the scratch tiers of the small alignment, queued segments
+        for a, b in ((3, 3), (31, 31), (32, 5), (5, 32), (31, 127), (2047, 1)):
+            tier = "nw_lds" if max(a, b) <= NW_SMALL else "nw_global"
+            add(f"lead{a}x{b}", {"lead_two_sided", tier}, n=90, largest=(a, b), length=90, identical=True, lead=(a, b))
+            add(f"trail{a}x{b}", {"trailing_two_sided", tier}, n=70, largest=(a, b), length=70, identical=True, trail=(a, b), runs=([(30, 2)], [(31, 1)]))
+            add(f"mid{a}x{b}", {tier}, n=64, largest=(a, b), length=64, identical=True, runs=([(33, a)], [(33, b)]))
+        add("lead_ref_only", {"lead_one_sided", "queued_one_sided"}, n=50, length=50, identical=True, lead=(40, 0), trail=(0, 3))
+        add("lead_qry_only", {"lead_one_sided", "trailing_run"}, n=50, length=50, identical=True, lead=(0, 40), trail=(5, 0))
+        add("long_one_sided", {"queued_one_sided"}, n=300, length=300, identical=True, runs=([(20, 32), (60, 33), (100, 64)], [(40, 65), (200, 5000)]))
+        add("members_7x3", {"lead_one_sided", "trailing_run", "queued_one_sided"}, members=(7, 3), length=(300, 280), lead=(0, 40), trail=(3, 0),
+            runs=([(100, 35), (200, 2)], [(150, 1)]))
+    elif group == "hand_back":     # pairs the device must hand back, between pairs it must not
+        add("ok_31x127", {"nw_global"}, n=80, largest=(31, 127), length=80, identical=True, runs=([(40, 31)], [(40, 127)]))
+        add("hb_32x127", {"hand_back"}, n=80, largest=(32, 127), hand_back=True, length=80, identical=True, runs=([(40, 32)], [(40, 127)], ), lead=(2, 2))
+        add("ok_members", {"trailing_run"}, members=(4, 2), length=(120, 130), trail=(0, 6), runs=([(50, 3)], [(60, 2)]))
+        add("hb_1x128", {"hand_back"}, n=80, largest=(1, 128), hand_back=True, length=80, identical=True, trail=(1, 128))
+        add("ok_2047x1", {"nw_global"}, n=60, largest=(2047, 1), length=60, identical=True, lead=(2047, 1))
+        add("hb_150x150", {"hand_back"}, n=80, largest=(150, 150), hand_back=True, length=80, identical=True, lead=(150, 150), runs=([(40, 3)], [(40, 3)]))
+        add("ok_tail", {"nw_lds"}, n=33, length=33, identical=True, runs=([(10, 3)], [(10, 4)]))
+    else:
+        raise ValueError(group)
+    return out

@@ -2,6 +2,14 @@
 
 The C++ mirror (twilight_amd/csrc/host/helpers.cpp) is what the end-to-end pins validate against the reference's MSAs; this test
 transfers that pin to the numpy restatement that the GPU tests of the device-resident level kernels use as their checker.
+
+test_numpy_restatement_matches_host_mirror_on_edge_shapes does the same on the directed shapes of level_cases.make_edge_case (runs behind
+the last kept column, a lead on one side only, two-sided runs up to 31 x 127, a removed run of 2 000 columns, 70 members, sides of 1-5
+and 1 025 columns, cached profiles of lengths that are no multiple of 4), which tests/test_gpu_level_edges.py sends through the kernels.
+
+Left out on purpose: a side whose EVERY column is removed (len > 0, reduced length 0).  The reference does not define it: it builds the
+all-gap path only for a side whose original length is 0 (alignment-cpu.cpp:89-90), so such a pair reaches Talco_xdrop::Align_freq with an
+empty profile inside `while (aln_wo_gc.empty())` (alignment-cpu.cpp:95), whose outcome the source leaves to chance.
 """
 import os
 import subprocess
@@ -31,7 +39,7 @@ def _hex(a):
     return " ".join(f"{int(x):08x}" for x in np.ascontiguousarray(a, dtype=np.float32).view(np.uint32).ravel())
 
 
-def _run_case(exe, tmp_path, case, tag):
+def _run_case(exe, tmp_path, case, tag, path=None):
     P = case.P
     f = tmp_path / f"{tag}.txt"
     with open(f, "w") as out:
@@ -43,7 +51,7 @@ def _run_case(exe, tmp_path, case, tag):
                 out.write(f"{w:.9g} {row.decode()}\n")
             if s.cache is not None:
                 out.write(_hex(s.cache) + "\n")
-        exp = LC.expected(case)
+        exp = LC.expected(case, path_wo_gc=path)
         out.write("path " + ("".join(str(int(c)) for c in exp["path_wo_gc"]) or "-") + "\n")
     r = subprocess.run([exe, str(f)], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
@@ -74,6 +82,39 @@ def test_numpy_restatement_matches_host_mirror(dump_exe, tmp_path, seq_type):
     for seed in range(6):
         case = LC.make_case(seq_type, seed, cached=(seed % 3), length=60 + 17 * seed)
         _run_case(dump_exe, tmp_path, case, f"{seq_type}{seed}")
+
+
+def edge_cases(seq_type):
+    """(tag, case, DP path or None for a random one).  Identical pairs take the all-match path, on which their runs meet."""
+    E = LC.make_edge_case
+    out = []
+
+    def ident(tag, n=40, **kw):
+        out.append((tag, E(seq_type, len(out), length=n, identical=True, **kw), np.zeros(n, dtype=np.int8)))
+
+    ident("trail_ref", trail=(7, 0))
+    ident("trail_qry", trail=(0, 7))
+    ident("trail_both", trail=(4, 6))
+    ident("lead_ref", lead=(9, 0))
+    ident("lead_qry", lead=(0, 9), trail=(2, 0))
+    for a, b in ((31, 31), (32, 5), (5, 32), (31, 127)):
+        ident(f"lead_{a}x{b}", lead=(a, b))
+        ident(f"run_{a}x{b}", runs=([(17, a)], [(17, b)]))
+        ident(f"trail_{a}x{b}", trail=(a, b))
+    ident("run_2000", runs=([(5, 2000)], [(30, 3)]))
+    for n in (1, 2, 3, 5, 1025):
+        out.append((f"len{n}", E(seq_type, 100 + n, members=(3, 2), length=(n, n + 1)), None))
+        ident(f"ident_len{n}", n=n, lead=(2, 0), trail=(1, 3))
+    out.append(("members70", E(seq_type, 7, members=(70, 4), length=(90, 75), lead=(0, 3), trail=(2, 0), runs=([(40, 2)], [(11, 5)]), thr=0.6), None))
+    for cached in (1, 2):
+        out.append((f"cached{cached}", E(seq_type, 20 + cached, members=(5, 3), length=(61, 83), lead=(2, 0), trail=(0, 4), runs=([(9, 3)], [(50, 2)]), cached=cached), None))
+    return out
+
+
+@pytest.mark.parametrize("seq_type", ["n", "p"])
+def test_numpy_restatement_matches_host_mirror_on_edge_shapes(dump_exe, tmp_path, seq_type):
+    for tag, case, path in edge_cases(seq_type):
+        _run_case(dump_exe, tmp_path, case, f"{seq_type}_{tag}", path=path)
 
 
 def test_matrix_tables_agree():

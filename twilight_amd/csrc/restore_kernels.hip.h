@@ -13,7 +13,10 @@
 //     (twilight_amd/csrc/host/helpers.cpp); a pair with a two-sided boundary too large for the per-thread scratch is flagged and
 //     restored by the host instead;
 //   * the output position of boundary a's segment is a + (lengths of the segments before it): one more scan (restore_write_kernel).
-// Checked against the host mirror on every level of the end-to-end tests (tests/test_gpu_level.py, tests/test_gpu_msa.py).
+// Checked bit for bit against oracle/level_oracle.py (itself held to the host mirror by tests/test_level_oracle_cpu.py): on the DP
+// paths of ordinary pairs by tests/test_gpu_level.py, and at the constants below at which a kernel changes behaviour (scan rounds,
+// write chunks, the LDS / global scratch tiers, hand-back, queued segments, a short out_stride, the batch size) by
+// tests/test_gpu_level_edges.py; the end-to-end tests (tests/test_gpu_msa.py) compare whole MSAs with the host mirror.
 #pragma once
 #include "level_kernels.hip.h"
 
@@ -41,7 +44,8 @@ struct RestoreArgs {
     int32_t *n_both;          // [n_sel] how many
     int32_t *wtot;            // [n_sel][n_wchunks] bytes of the final path per chunk of boundaries (restore_count_kernel -> restore_write_kernel)
     int32_t n_wchunks;
-    int8_t *arena;            // [n_sel][out_stride] the aligned two-sided segments, reversed
+    int8_t *arena;            // [n_sel][arena_stride] the aligned two-sided segments, reversed
+    int32_t arena_stride;     // >= both sides' original columns together (all the two-sided runs of a pair can add up to), whatever out_stride is
     int32_t bstride;
     int8_t *out;              // [n_pairs][out_stride] final paths
     int32_t out_stride;
@@ -212,7 +216,7 @@ __global__ void __launch_bounds__(kNwThreads) restore_align_kernel(RestoreArgs a
     int32_t *seg = a.seg + (size_t)blockIdx.x * a.bstride;
     const int32_t *aoff = a.aoff + (size_t)blockIdx.x * a.bstride;
     const uint8_t *cR = a.colinfo + (size_t)(2 * pair) * a.stride, *cQ = cR + a.stride;
-    int8_t *arena = a.arena + (size_t)blockIdx.x * a.out_stride;
+    int8_t *arena = a.arena + (size_t)blockIdx.x * a.arena_stride;
     const size_t thr = ((size_t)blockIdx.x * gridDim.y + blockIdx.y) * kNwThreads + threadIdx.x;
     int8_t *tb = a.tbs + thr * kNwCells;
     float *rw = a.rows + thr * (6 * kNwRow);
@@ -276,7 +280,7 @@ __global__ void __launch_bounds__(kRsThreads) restore_write_kernel(RestoreArgs a
     const int8_t *path = a.aln + (size_t)pair * a.aln_stride;
     const int32_t *runR = a.run + (size_t)blockIdx.x * 4 * a.bstride, *runQ = runR + a.bstride;
     const int32_t *seg = a.seg + (size_t)blockIdx.x * a.bstride, *aoff = a.aoff + (size_t)blockIdx.x * a.bstride;
-    const int8_t *arena = a.arena + (size_t)blockIdx.x * a.out_stride;
+    const int8_t *arena = a.arena + (size_t)blockIdx.x * a.arena_stride;
     int8_t *out = a.out + (size_t)pair * a.out_stride;
     int base = 0;
     for (int c = 0; c < (int)blockIdx.y; ++c) base += a.wtot[(size_t)blockIdx.x * a.n_wchunks + c];
@@ -302,6 +306,7 @@ __global__ void __launch_bounds__(kRsThreads) restore_write_kernel(RestoreArgs a
     // Segments of up to kSegDirect bytes are written by the boundary's own thread; a removed run can be thousands of columns long (one
     // thread would write it byte by byte while the launch waits): those are queued and filled by the whole workgroup.
     constexpr int kSegDirect = 32, kQueue = 2048;
+    static_assert(kRsThreads * kWrItems <= kQueue, "every boundary of a chunk finds a queue slot");
     __shared__ int q_n, q_pos[kQueue], q_len[kQueue], q_src[kQueue];       // q_src >= 0: arena offset (reversed copy); -1 / -2: fill with code 1 / 2
     if (threadIdx.x == 0) q_n = 0;
     __syncthreads();
@@ -313,8 +318,7 @@ __global__ void __launch_bounds__(kRsThreads) restore_write_kernel(RestoreArgs a
         if (pos + w <= a.out_stride) {
             if (sl[k] > 0) {
                 const bool both = src[k] >= 0;
-                int slot = -1;
-                if (sl[k] > kSegDirect) { slot = atomicAdd(&q_n, 1); if (slot >= kQueue) slot = -1; }
+                const int slot = (sl[k] > kSegDirect) ? atomicAdd(&q_n, 1) : -1;
                 if (slot >= 0) { q_pos[slot] = pos; q_len[slot] = sl[k]; q_src[slot] = src[k]; }
                 else if (both) { const int8_t *from = arena + src[k]; for (int t = 0; t < sl[k]; ++t) out[pos + t] = from[sl[k] - 1 - t]; }
                 else { const int8_t code = (src[k] == -2) ? 2 : 1; for (int t = 0; t < sl[k]; ++t) out[pos + t] = code; }
@@ -324,7 +328,7 @@ __global__ void __launch_bounds__(kRsThreads) restore_write_kernel(RestoreArgs a
         pos += w;
     }
     __syncthreads();
-    const int nq = min(q_n, kQueue);
+    const int nq = q_n;
     const int lane = threadIdx.x & 63;
     for (int e = threadIdx.x >> 6; e < nq; e += kRsWaves) {      // a wave per queued segment
         const int p0 = q_pos[e], len = q_len[e], from = q_src[e];

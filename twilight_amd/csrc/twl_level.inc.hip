@@ -889,7 +889,8 @@ static int restore_batch(twl_store *s, const twl_params *p, int32_t n_sel, const
     if ((rc = lv->r_nboth.ensure(ns * sizeof(int32_t)))) return rc;
     const unsigned nWch = (unsigned)((bstride + (size_t)twl::kRsThreads * twl::kWrItems - 1) / ((size_t)twl::kRsThreads * twl::kWrItems));      // chunks of boundaries of the longest possible path
     if ((rc = lv->r_wtot.ensure(ns * nWch * sizeof(int32_t)))) return handBack(rc);
-    if ((rc = lv->r_arena.ensure(ns * (size_t)out_stride))) return handBack(rc);
+    // (the arena's pitch does not follow out_stride: the two-sided runs of a pair add up to at most both sides' columns, however short the caller's rows are)
+    if ((rc = lv->r_arena.ensure(ns * 2 * sl))) return handBack(rc);
     if ((rc = lv->r_outlen.ensure((size_t)n * sizeof(int32_t)))) return rc;
     const unsigned nb = (unsigned)std::max(1, std::min(128, 4096 / n_sel));     // one-wave workgroups per pair of the small alignments (<= ~1.8 GB of scratch for the rare large ones)
     if ((rc = lv->r_tb.ensure(ns * nb * twl::kNwThreads * (size_t)twl::kNwCells))) return handBack(rc);
@@ -902,7 +903,7 @@ static int restore_batch(twl_store *s, const twl_params *p, int32_t n_sel, const
     a.orig_idx = (int32_t *)lv->r_oidx.p; a.run = (int32_t *)lv->r_run.p; a.seg = (int32_t *)lv->r_seg.p; a.aoff = (int32_t *)lv->r_aoff.p;
     a.both_list = (int32_t *)lv->r_blist.p; a.n_both = (int32_t *)lv->r_nboth.p;
     a.wtot = (int32_t *)lv->r_wtot.p; a.n_wchunks = (int32_t)nWch;
-    a.arena = (int8_t *)lv->r_arena.p; a.bstride = (int32_t)bstride;
+    a.arena = (int8_t *)lv->r_arena.p; a.arena_stride = (int32_t)(2 * sl); a.bstride = (int32_t)bstride;
     a.out = (int8_t *)lv->d_paths.p; a.out_stride = out_stride; a.out_len = (int32_t *)lv->r_outlen.p;
     a.tbs = (int8_t *)lv->r_tb.p; a.rows = (float *)lv->r_rows.p;
     a.ms = p->P - 1;

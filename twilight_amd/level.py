@@ -224,6 +224,11 @@ class Store:
         api._check(_lib().twl_level_read_final(self._h, C.c_int32(pair), out.ctypes.data_as(C.POINTER(C.c_int8)), C.c_int32(length)))
         return out[:length]
 
+    def write_final(self, pair: int, path: np.ndarray):
+        """twl_level_write_final: the final path of a pair the device handed back (-1), restored by the caller, into the level's path buffer."""
+        p = np.ascontiguousarray(path, dtype=np.int8)
+        api._check(_lib().twl_level_write_final(self._h, C.c_int32(pair), p.ctypes.data_as(C.POINTER(C.c_int8)), C.c_int32(len(p))))
+
     def commit_from_dp(self, paths: Sequence[Optional[np.ndarray]], path_len: Sequence[int], stride: Optional[int] = None, restored: Sequence[int] = ()):
         """twl_level_commit_from_dp: paths[i] is None -> pair i's path is in HBM already (the DP output, or what twl_level_restore made of it), path_len[i] long."""
         n = self._n_pairs

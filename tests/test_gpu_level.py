@@ -470,3 +470,95 @@ def test_leaf_level_runs_the_step_without_gap_terms_and_division(gpu):
     st.align(p)
     assert b", 0, 1>" not in twl.get_stats(0).kernel
     st.close()
+
+
+def test_rejected_prepare_leaves_no_stored_profile_behind(gpu):
+    """A prepare that is rejected for a LATER side (member 99) must not keep the profile an earlier side asked to store (store_id 3): the corrected call
+    succeeds and stores it.  An argument error: it returns before any kernel is launched."""
+    import copy
+
+    import twilight_amd as twl
+    from twilight_amd import level as L
+
+    a, b = LC.make_case("n", 31, cached=0, length=200), LC.make_case("n", 32, cached=0, length=260)
+    seqs, pairs, ids = _level([a, b])
+    pairs[0][0].store_id = 3
+    bad = copy.deepcopy(pairs)
+    bad[1][1].members = list(bad[1][1].members[:-1]) + [99]
+    p = twl.make_params(LC.matrix_of("n"))
+    st = L.Store(seqs, "n")
+    with pytest.raises(twl.TwlError, match="member sequence id out of range"):
+        st.prepare(p, bad)
+    with pytest.raises(twl.TwlError, match="unknown cache id"):
+        st.cache(3)
+    st.prepare(p, pairs)
+    want = LO.cache_from_profile(LC.side_profile(a, 0), a.sides[0].group_weight, len(a.sides[0].rows))
+    assert np.array_equal(_bits(st.cache(3)), _bits(want))
+    st.close()
+
+
+_CHILD_REJECTED_CREATE = r"""
+import ctypes as C, sys
+sys.path[:0] = [{root!r}, {tests!r}]
+import numpy as np
+import twilight_amd as twl
+from twilight_amd import api, level, synth
+import oracle_lib as O
+
+twl.init([0])
+lib = level._lib()
+seqs = (C.c_char_p * 2)(b"ACGT", b"AC")
+lens = (C.c_int32 * 2)(4, -1)
+h = C.c_void_p()
+try:
+    api._check(lib.twl_store_create(C.c_int(0), C.c_char(b"n"), C.c_int32(2), seqs, lens, C.byref(h)))
+    raise SystemExit("a negative length was accepted")
+except twl.TwlError as e:
+    assert "negative sequence length" in str(e), e
+twl.shutdown()
+twl.init([0])
+M = synth.nucleotide_matrix()
+batch = synth.make_level_batch(6, 700, members=((1, 4), (1, 4)), seed=7)
+aln, n, err = twl.align_batch(twl.make_params(M), batch)
+oa, on, oerr, _ = O.align_batch(O.make_params(M), batch, threads=2)
+assert np.array_equal(err, oerr) and np.array_equal(n, on) and all(np.array_equal(aln[i, : n[i]], oa[i, : on[i]]) for i in range(batch.n_pairs))
+twl.shutdown()
+print("child ok")
+"""
+
+
+def test_rejected_store_create_does_not_hold_the_library_up(gpu):
+    """twl_store_create with a negative length is rejected (no kernel is launched) and must leave the device's store count as it was: twl_shutdown then
+    shuts the library down, and a second twl_init aligns a small batch.  One fresh child process (shutdown is process-wide), under its own time limit."""
+    import subprocess
+
+    code = _CHILD_REJECTED_CREATE.format(root=ROOT, tests=os.path.join(ROOT, "tests"))
+    r = subprocess.run(["timeout", "-k", "10", "300", sys.executable, "-c", code], capture_output=True, text=True, timeout=330)
+    assert r.returncode == 0 and "child ok" in r.stdout, r.stdout + r.stderr
+    assert "still alive" not in r.stderr, r.stderr
+
+
+def test_row_mover_lists_blocks_zero_length_rows_and_a_growing_pitch(gpu):
+    """twl_store_read_rows_of / _write_rows / _rows_to_block / _rows_from_block on ONE store, against the bytes on the Python side: ids in no order, a row
+    of length zero read and written, and a write longer than the row pitch (8 x 400 + 256 columns at creation)."""
+    from twilight_amd import level as L
+
+    rng = np.random.default_rng(17)
+    mk = lambda n: bytes(rng.choice(list(b"ACGT-"), size=n).astype(np.uint8))
+    seqs = [mk(int(rng.integers(40, 400))) for _ in range(12)] + [b"", mk(400)]
+    st = L.Store(seqs, "n")
+    ids = [7, 12, 2, 13, 11, 0]
+    assert st.rows_of(ids) == [seqs[i] for i in ids]
+    assert st.rows_to_block(ids) == [seqs[i] for i in ids]
+    assert st.rows_of([12]) == [b""] and st.rows_of([]) == []
+    new = [mk(5000), mk(3), b"", mk(9000), mk(1), mk(777)]                      # 5000, then 9000 columns: past the pitch (and the grown one), once per way in
+    st.write_rows(ids[:3], new[:3])
+    assert st.rows_of(ids[:3]) == new[:3]
+    st.write_rows(ids[3:], new[3:], via_device_block=True)
+    want = list(seqs)
+    for i, r in zip(ids, new):
+        want[i] = r
+    assert st.rows() == want
+    assert st.rows_of(ids) == new and st.rows_to_block(ids) == new
+    assert st.rows_of(ids[::-1]) == new[::-1]
+    st.close()

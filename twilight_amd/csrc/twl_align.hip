@@ -184,7 +184,7 @@ int check_params(const twl_params *p)
 
 }  // namespace
 
-static void twl_level_pool_release(Device *d);      // twl_level.inc.hip: the level buffers the device lent to its stores
+static void twl_level_pool_release(Device *d);      // twl_store.inc.hip: the level buffers the device lent to its stores
 namespace { extern int g_fail_next_row_allocs; void comm_destroy_raw(void *comm); }
 
 extern "C" {
@@ -632,5 +632,7 @@ int twl_get_pair_cells(int device, uint64_t *cells_out, int32_t n)
 
 }  // extern "C"
 
+#include "twl_level_plan.inc.hip"
+#include "twl_store.inc.hip"
 #include "twl_level.inc.hip"
 #include "twl_place.inc.hip"

@@ -1,5 +1,5 @@
 // twilight_amd/csrc/twl_place.inc.hip -- host side of placement without a tree (include/twl_place.h).
-// Included at the end of twl_align.hip, behind twl_level.inc.hip: it works on that file's stores and level buffers.
+// Included at the end of twl_align.hip, behind twl_store.inc.hip and twl_level.inc.hip: it works on their stores and level buffers.
 //
 // HBM of a placement: one arena of final paths (a slot of L + len bytes per sequence of the store), longest[L + 1], and at the finish
 // ins[L + 1] and colsrc[W] (kernels: place_kernels.hip.h).
@@ -14,34 +14,10 @@ struct twl_place {
     std::vector<int64_t> slot;       // its slot in the arena
     std::vector<int32_t> plen;       // collected path length, -1: not collected
     std::vector<int32_t> placed;     // collected ids, in order
-    Buf arena, longest, ins, colsrc, w, bad, tab, hostRows;
+    Buf arena, longest, ins, colsrc, w, bad, hostRows;
+    Arena up;                        // the small per-call tables of collect / finish: both synchronise the stream before they return
     PinBuf back;
 };
-
-namespace {
-
-// the small per-call tables, back to back in one upload (tab): returns the device address of each
-struct TabUp {
-    std::vector<char> h;
-    std::vector<size_t> at;
-    template <class T> size_t put(const std::vector<T> &v)
-    {
-        const size_t o = (h.size() + 255) & ~(size_t)255;
-        h.resize(o + std::max<size_t>(v.size() * sizeof(T), 16));
-        if (!v.empty()) memcpy(h.data() + o, v.data(), v.size() * sizeof(T));
-        return o;
-    }
-    int flush(Buf &b, hipStream_t st)
-    {
-        int rc = b.ensure(std::max<size_t>(h.size(), 256));
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(b.p, h.data(), h.size(), hipMemcpyHostToDevice, st));
-        return TWL_OK;
-    }
-};
-template <class T> T *at(Buf &b, size_t off) { return reinterpret_cast<T *>((char *)b.p + off); }
-
-}  // namespace
 
 extern "C" {
 
@@ -50,51 +26,46 @@ int twl_store_count_columns(twl_store *s, int32_t n_ids, const int32_t *ids, int
     if (!s || n_ids < 1 || !ids || cache_id < 0) { g_err = "bad argument"; return TWL_ERR_BAD_ARGUMENT; }
     if (s->cache.count(cache_id)) { g_err = "cache id in use"; return TWL_ERR_BAD_ARGUMENT; }
     const int32_t L = (ids[0] >= 0 && ids[0] < s->n_seqs) ? s->len[ids[0]] : -1;
-    std::vector<int32_t> idv(ids, ids + n_ids);
     for (int32_t t = 0; t < n_ids; ++t) {
         if (ids[t] < 0 || ids[t] >= s->n_seqs) { g_err = "sequence id out of range"; return TWL_ERR_BAD_ARGUMENT; }
         if (s->len[ids[t]] != L) { g_err = "the rows to count differ in length"; return TWL_ERR_BAD_ARGUMENT; }
     }
-    Device *d = s->d;
-    std::lock_guard<std::mutex> lk(d->mu);
-    HIP_TRY(hipSetDevice(d->id));
-    hipStream_t st = d->stream;
+    DEVICE_CALL(call, s->d);
+    hipStream_t st = call.st;
     const size_t P = (size_t)s->P, cells = (size_t)L * P;
-    auto *e = new CacheEntry();
-    int rc = cache_buf_get(d, e->buf, std::max<size_t>(cells * sizeof(float), 16));
-    if (rc) { delete e; return rc; }
-    e->len = L;
-    Buf counts;
-    if ((rc = counts.ensure(std::max<size_t>(cells * sizeof(int32_t), 16)))) { cache_buf_put(d, e->buf); delete e; return rc; }
-    if (s->rows_event) { HIP_TRY(hipStreamWaitEvent(st, s->rows_event, 0)); s->rows_event = nullptr; }
-    if ((rc = upload(s->d_plane, s->plane, st))) { cache_buf_put(d, e->buf); delete e; return rc; }
-    if ((rc = s->d_gather.ensure((size_t)n_ids * sizeof(int32_t) + 64))) { cache_buf_put(d, e->buf); delete e; return rc; }
-    HIP_TRY(hipMemcpyAsync(s->d_gather.p, idv.data(), (size_t)n_ids * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    CacheEntry e;
+    int rc = e.take(call.d, L, std::max<size_t>(cells * sizeof(float), 16));
+    if (rc) return rc;
+    struct Scratch { Buf b; ~Scratch() { b.release(); } } scratch;      // the integer counts: freed behind the call's synchronisation
+    Buf &counts = scratch.b;
+    if ((rc = counts.ensure(std::max<size_t>(cells * sizeof(int32_t), 16)))) return rc;
+    if ((rc = wait_rows(s, st))) return rc;
+    RowRefs r;
+    if ((rc = upload_row_tables(s, st, n_ids, ids, nullptr, nullptr, r))) return rc;
     if (cells) {
         HIP_TRY(hipMemsetAsync(counts.p, 0, cells * sizeof(int32_t), st));
         const dim3 grid((unsigned)((L + twl::kPlThreads - 1) / twl::kPlThreads), (unsigned)((n_ids + twl::kCountRows - 1) / twl::kCountRows));
         if (s->P == 6)
             hipLaunchKernelGGL(twl::count_columns_kernel<6>, grid, dim3(twl::kPlThreads), 0, st, (const char *)s->rows[0].p, (const char *)s->rows[1].p, s->cap,
-                               (const uint8_t *)s->d_plane.p, (const int32_t *)s->d_gather.p, n_ids, L, (const uint8_t *)s->lut.p, (int32_t *)counts.p);
+                               r.plane.as<const uint8_t>(), r.ids.as<const int32_t>(), n_ids, L, (const uint8_t *)s->lut.p, (int32_t *)counts.p);
         else
             hipLaunchKernelGGL(twl::count_columns_kernel<22>, grid, dim3(twl::kPlThreads), 0, st, (const char *)s->rows[0].p, (const char *)s->rows[1].p, s->cap,
-                               (const uint8_t *)s->d_plane.p, (const int32_t *)s->d_gather.p, n_ids, L, (const uint8_t *)s->lut.p, (int32_t *)counts.p);
+                               r.plane.as<const uint8_t>(), r.ids.as<const int32_t>(), n_ids, L, (const uint8_t *)s->lut.p, (int32_t *)counts.p);
         hipLaunchKernelGGL(twl::counts_to_cache_kernel, dim3((unsigned)((cells + twl::kPlThreads - 1) / twl::kPlThreads)), dim3(twl::kPlThreads), 0, st,
-                           (const int32_t *)counts.p, (int64_t)cells, (float *)e->buf.p);
+                           (const int32_t *)counts.p, (int64_t)cells, (float *)e.buf.p);
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipStreamSynchronize(st));
-    s->cache[cache_id] = e;
+    s->cache[cache_id] = std::move(e);
     return TWL_OK;
 }
 
 int twl_place_create(twl_store *s, int32_t L, twl_place **out)
 {
     if (!s || L < 0 || !out) { g_err = "bad argument"; return TWL_ERR_BAD_ARGUMENT; }
-    Device *d = s->d;
-    std::lock_guard<std::mutex> lk(d->mu);
-    HIP_TRY(hipSetDevice(d->id));
-    std::unique_ptr<twl_place> pl(new twl_place());
+    DEVICE_CALL(call, s->d);
+    Device *d = call.d;
+    auto pl = std::make_unique<twl_place>();
     pl->s = s;
     pl->L = L;
     pl->qlen = s->len;
@@ -114,14 +85,15 @@ int twl_place_create(twl_store *s, int32_t L, twl_place **out)
 void twl_place_destroy(twl_place *pl)
 {
     if (!pl) return;
+    const std::unique_ptr<twl_place> own(pl);
     {
         std::lock_guard<std::mutex> lk(pl->s->d->mu);
         (void)hipSetDevice(pl->s->d->id);
         (void)hipStreamSynchronize(pl->s->d->stream);
-        for (Buf *b : {&pl->arena, &pl->longest, &pl->ins, &pl->colsrc, &pl->w, &pl->bad, &pl->tab, &pl->hostRows}) b->release();
+        for (Buf *b : {&pl->arena, &pl->longest, &pl->ins, &pl->colsrc, &pl->w, &pl->bad, &pl->hostRows}) b->release();
+        pl->up.release();
         pl->back.release();
     }
-    delete pl;
 }
 
 int twl_place_collect(twl_place *pl, twl_store *s, int32_t n_pairs, const int32_t *seq_ids, const int8_t *paths, const int32_t *path_len,
@@ -152,10 +124,8 @@ int twl_place_collect(twl_place *pl, twl_store *s, int32_t n_pairs, const int32_
         if (w == 0) { srcOff.push_back((int64_t)hostRows.size() * path_stride); hostRows.push_back(i); }
         else srcOff.push_back((int64_t)i * (w == 1 ? dpStride : (int64_t)path_stride));
     }
-    Device *d = s->d;
-    std::lock_guard<std::mutex> lk(d->mu);
-    HIP_TRY(hipSetDevice(d->id));
-    hipStream_t st = d->stream;
+    DEVICE_CALL(call, s->d);
+    hipStream_t st = call.st;
     int rc;
     const int32_t m = (int32_t)ids.size();
     if (m > 0) {
@@ -165,19 +135,21 @@ int twl_place_collect(twl_place *pl, twl_store *s, int32_t n_pairs, const int32_
                 HIP_TRY(hipMemcpyAsync((int8_t *)pl->hostRows.p + k * (size_t)path_stride, paths + (size_t)hostRows[k] * (size_t)path_stride,
                                        (size_t)path_len[hostRows[k]], hipMemcpyHostToDevice, st));
         }
-        TabUp up;
-        const size_t oWhich = up.put(which), oSrc = up.put(srcOff), oPlen = up.put(plen), oQlen = up.put(qlen), oDst = up.put(dstOff);
-        if ((rc = up.flush(pl->tab, st))) return rc;
+        Ref rWhich, rSrc, rPlen, rQlen, rDst;
+        Arena &A = pl->up;
+        if ((rc = A.begin((size_t)m * (1 + 2 * sizeof(int64_t) + 2 * sizeof(int32_t)), 5))) return rc;
+        A.put(rWhich, which); A.put(rSrc, srcOff); A.put(rPlen, plen); A.put(rQlen, qlen); A.put(rDst, dstOff);
+        if ((rc = A.flush(st))) return rc;
         if ((rc = pl->bad.ensure((size_t)m * sizeof(int32_t)))) return rc;
         twl::CollectArgs a{};
         a.src[0] = (const int8_t *)pl->hostRows.p;
         a.src[1] = from_dp ? (const int8_t *)s->lv->d_aln.p : nullptr;
         a.src[2] = from_dp ? (const int8_t *)s->lv->d_paths.p : nullptr;
-        a.which = at<const uint8_t>(pl->tab, oWhich);
-        a.src_off = at<const int64_t>(pl->tab, oSrc);
-        a.plen = at<const int32_t>(pl->tab, oPlen);
-        a.qlen = at<const int32_t>(pl->tab, oQlen);
-        a.dst_off = at<const int64_t>(pl->tab, oDst);
+        a.which = rWhich.as<const uint8_t>();
+        a.src_off = rSrc.as<const int64_t>();
+        a.plen = rPlen.as<const int32_t>();
+        a.qlen = rQlen.as<const int32_t>();
+        a.dst_off = rDst.as<const int64_t>();
         a.arena = (int8_t *)pl->arena.p;
         a.longest = (int32_t *)pl->longest.p;
         a.bad = (int32_t *)pl->bad.p;
@@ -216,10 +188,8 @@ int twl_place_finish(twl_place *pl, int32_t n_backbone, const int32_t *backbone_
     }
     for (int32_t id : pl->placed)
         if (s->len[id] != pl->qlen[id]) { g_err = "a placed sequence's row has been rewritten since it was collected"; return TWL_ERR_BAD_ARGUMENT; }
-    Device *d = s->d;
-    std::lock_guard<std::mutex> lk(d->mu);
-    HIP_TRY(hipSetDevice(d->id));
-    hipStream_t st = d->stream;
+    DEVICE_CALL(call, s->d);
+    hipStream_t st = call.st;
     int rc;
     if ((rc = pl->ins.ensure(((size_t)L + 1) * sizeof(int32_t)))) return rc;
     if ((rc = pl->w.ensure(sizeof(int32_t)))) return rc;
@@ -230,7 +200,7 @@ int twl_place_finish(twl_place *pl, int32_t n_backbone, const int32_t *backbone_
     HIP_TRY(hipStreamSynchronize(st));
     const int32_t W = *(const int32_t *)pl->back.p;
     if (W < L) { g_err = "final width below the backbone's"; return TWL_ERR_HIP; }
-    if (s->rows_event) { HIP_TRY(hipStreamWaitEvent(st, s->rows_event, 0)); s->rows_event = nullptr; }
+    if ((rc = wait_rows(s, st))) return rc;
     if ((rc = grow_rows(s, (int64_t)W + 1))) return rc;
     if ((rc = pl->colsrc.ensure((size_t)std::max(W, 1) * sizeof(int32_t)))) return rc;
     HIP_TRY(hipMemsetAsync(pl->colsrc.p, 0xFF, (size_t)std::max(W, 1) * sizeof(int32_t), st));
@@ -243,9 +213,11 @@ int twl_place_finish(twl_place *pl, int32_t n_backbone, const int32_t *backbone_
     std::vector<int64_t> pOff;
     for (int32_t id : pIds) { pPlane.push_back(s->plane[id]); pQlen.push_back(pl->qlen[id]); pPlen.push_back(pl->plen[id]); pOff.push_back(pl->slot[id]); }
     for (int32_t id : bIds) bPlane.push_back(s->plane[id]);
-    TabUp up;
-    const size_t oPId = up.put(pIds), oPPl = up.put(pPlane), oPQ = up.put(pQlen), oPOff = up.put(pOff), oPLen = up.put(pPlen), oBId = up.put(bIds), oBPl = up.put(bPlane);
-    if ((rc = up.flush(pl->tab, st))) return rc;
+    Ref rPId, rPPl, rPQ, rPOff, rPLen, rBId, rBPl;
+    Arena &A = pl->up;
+    if ((rc = A.begin((size_t)nP * (1 + sizeof(int64_t) + 3 * sizeof(int32_t)) + (size_t)n_backbone * (1 + sizeof(int32_t)), 7))) return rc;
+    A.put(rPId, pIds); A.put(rPPl, pPlane); A.put(rPQ, pQlen); A.put(rPOff, pOff); A.put(rPLen, pPlen); A.put(rBId, bIds); A.put(rBPl, bPlane);
+    if ((rc = A.flush(st))) return rc;
     twl::ExpandArgs a{};
     a.rows0 = (const char *)s->rows[0].p; a.rows1 = (const char *)s->rows[1].p;
     a.out0 = (char *)s->rows[0].p; a.out1 = (char *)s->rows[1].p;
@@ -255,13 +227,13 @@ int twl_place_finish(twl_place *pl, int32_t n_backbone, const int32_t *backbone_
     a.L = L; a.W = W;
     if (nP > 0) {
         twl::ExpandArgs ap = a;
-        ap.ids = at<const int32_t>(pl->tab, oPId); ap.plane = at<const uint8_t>(pl->tab, oPPl); ap.qlen = at<const int32_t>(pl->tab, oPQ);
-        ap.path_off = at<const int64_t>(pl->tab, oPOff); ap.plen = at<const int32_t>(pl->tab, oPLen);
+        ap.ids = rPId.as<const int32_t>(); ap.plane = rPPl.as<const uint8_t>(); ap.qlen = rPQ.as<const int32_t>();
+        ap.path_off = rPOff.as<const int64_t>(); ap.plen = rPLen.as<const int32_t>();
         hipLaunchKernelGGL(twl::place_expand_kernel, dim3((unsigned)nP), dim3(twl::kPlThreads), 0, st, ap);
     }
     if (n_backbone > 0 && W > 0) {
         twl::ExpandArgs ab = a;
-        ab.ids = at<const int32_t>(pl->tab, oBId); ab.plane = at<const uint8_t>(pl->tab, oBPl);
+        ab.ids = rBId.as<const int32_t>(); ab.plane = rBPl.as<const uint8_t>();
         hipLaunchKernelGGL(twl::backbone_expand_kernel, dim3((unsigned)n_backbone, (unsigned)((W + twl::kPlThreads - 1) / twl::kPlThreads)), dim3(twl::kPlThreads), 0, st, ab);
     }
     HIP_TRY(hipGetLastError());
@@ -276,11 +248,9 @@ int twl_place_finish(twl_place *pl, int32_t n_backbone, const int32_t *backbone_
 int twl_place_read_insertions(twl_place *pl, int32_t *out)
 {
     if (!pl || !out) { g_err = "bad argument"; return TWL_ERR_BAD_ARGUMENT; }
-    Device *d = pl->s->d;
-    std::lock_guard<std::mutex> lk(d->mu);
-    HIP_TRY(hipSetDevice(d->id));
-    HIP_TRY(hipMemcpyAsync(out, pl->longest.p, ((size_t)pl->L + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(hipStreamSynchronize(d->stream));
+    DEVICE_CALL(call, pl->s->d);
+    HIP_TRY(hipMemcpyAsync(out, pl->longest.p, ((size_t)pl->L + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, call.st));
+    HIP_TRY(hipStreamSynchronize(call.st));
     return TWL_OK;
 }
 

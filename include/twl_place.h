@@ -47,7 +47,9 @@ void twl_place_destroy(twl_place *pl);
  *   from_dp[i] == 2   row i of the level's path buffer (twl_level_restore, or twl_level_write_final), path_stride = the restore's pitch
  *   from_dp[i] == 0   paths + i * path_stride, from the host (from_dp == NULL: every row; no level needed then)
  * path_len[i] == 0 skips pair i.  Each path must hold exactly L codes != 1 and len(sequence) codes != 2.  The paths are kept in the
- * placement, their insertions folded into longest[]; no row is rewritten and no cache merged.  With from_dp given, the level ends here
+ * placement, their insertions folded into longest[]; no row is rewritten and no cache merged.  A path of another shape is refused: the
+ * call fails, nothing of that path is folded in and its sequence may be collected again, while the well-formed paths of the same call
+ * stay collected (collecting one of them again is refused as collected twice).  With from_dp given, the level ends here
  * (its buffers go back to the device as at a commit): the next chunk of pairs starts with twl_level_prepare.
  */
 int twl_place_collect(twl_place *pl, twl_store *s, int32_t n_pairs, const int32_t *seq_ids, const int8_t *paths, const int32_t *path_len,

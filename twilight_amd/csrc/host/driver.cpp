@@ -30,7 +30,7 @@ static int effectiveCpus()
 
 static bool flag(const char *a, const char *s, const char *l) { return (s && !strcmp(a, s)) || (l && !strcmp(a, l)); }
 
-bool parseCommandLine(int argc, char **argv, Option &o, bool allowPlacement)
+bool parseCommandLine(int argc, char **argv, Option &o, bool allowPlacement, bool allowMerge)
 {
     bool typeGiven = false;
     o.cpuNum = 0;
@@ -73,11 +73,18 @@ bool parseCommandLine(int argc, char **argv, Option &o, bool allowPlacement)
         else if (flag(a, nullptr, "--test-fork-host-staged")) o.testForkHostStaged = true;
         else if (allowPlacement && flag(a, "-a", "--alignment")) o.backboneAlnFile = val();
         else if (allowPlacement && flag(a, nullptr, "--test-place-chunk")) o.testPlaceChunk = std::max(0, atoi(val()));
+        else if (allowMerge && flag(a, "-f", "--files")) o.msaDir = val();
         else if (flag(a, nullptr, "--overwrite")) {}
         else if (flag(a, "-h", "--help")) return false;
         else { std::cerr << "ERROR: unsupported option " << a << " (this build covers the tree+sequences alignment mode only)\n"; exit(1); }
     }
-    if (!o.backboneAlnFile.empty()) {      // placement (reference option.cpp:15-22): -a -i -o without -t
+    if (!o.msaDir.empty()) {               // merge (reference option.cpp: -f -o, nothing else to read)
+        if (!o.treeFile.empty() || !o.seqFile.empty() || !o.backboneAlnFile.empty()) { std::cerr << "ERROR: -f (merging alignments) cannot be combined with -t, -i or -a.\n"; exit(1); }
+        if (o.outFile.empty()) return false;
+        if (o.hostStaged) { std::cerr << "ERROR: --host-staged is not available in merge mode (-f).\n"; exit(1); }
+        if (o.gpuIdx.size() > 1 || o.gpuNum > 1) { std::cerr << "ERROR: merge mode (-f) runs on one GPU: give at most one --gpu-index.\n"; exit(1); }
+        o.alnMode = MERGE_MSA;
+    } else if (!o.backboneAlnFile.empty()) {      // placement (reference option.cpp:15-22): -a -i -o without -t
         if (!o.treeFile.empty()) { std::cerr << "ERROR: -a together with -t (placement with a tree) is not supported yet.\n"; exit(1); }
         if (o.seqFile.empty() || o.outFile.empty()) return false;
         if (o.hostStaged) { std::cerr << "ERROR: --host-staged is not available in placement mode (-a).\n"; exit(1); }
@@ -90,7 +97,8 @@ bool parseCommandLine(int argc, char **argv, Option &o, bool allowPlacement)
     }
     if (o.gappyVertical > 1 || o.gappyVertical <= 0) { std::cerr << "ERROR: Invalid value for --remove-gappy. The value of --remove-gappy should be in (0,1]\n"; exit(1); }
     if (o.gpuIdx.empty() && o.gpuNum > 0) for (int g = 0; g < o.gpuNum; ++g) o.gpuIdx.push_back(g);
-    if (!typeGiven) o.type = io::detectType(o.seqFile);
+    o.typeGiven = typeGiven;
+    if (!typeGiven && o.alnMode != MERGE_MSA) o.type = io::detectType(o.seqFile);      // (a merge takes it from its first file: merge.cpp)
     const int maxCpu = effectiveCpus();
     if (o.cpuNum <= 0 || o.cpuNum > maxCpu) o.cpuNum = maxCpu;       // -C/--cpu, default: all usable cores (option.cpp:41-46)
     omp_set_num_threads(o.cpuNum);

@@ -1,6 +1,7 @@
 // twilight_amd/csrc/host/main.cpp -- `twilight-mi355x`: TWILIGHT's tree+sequences mode with the MI355X level kernel.
 //   twilight-mi355x -t tree.nwk -i seqs.fa -o out.aln [-v] [--check] [--gpu-index 0,1,...] [scoring flags as in TWILIGHT]
 //   twilight-mi355x -a backbone.aln -i new.fa -o out.aln [...]   (built with TWL_PLACE: placement without a tree, place.cpp)
+//   twilight-mi355x -f DIR -o out.aln [...]                      (built with TWL_MERGE: the alignments of a directory merged, merge.cpp)
 #include "twl_host.hpp"
 
 #include "../../../include/twl_align.h"
@@ -53,12 +54,27 @@ int main(int argc, char **argv)
 #else
     const bool placement = false;
 #endif
-    if (!msa::parseCommandLine(argc, argv, option, placement)) {
+#ifdef TWL_MERGE
+    const bool merging = true;
+#else
+    const bool merging = false;
+#endif
+    if (!msa::parseCommandLine(argc, argv, option, placement, merging)) {
         std::cerr << "usage: twilight-mi355x -t <tree.nwk> -i <sequences.fa[.gz]> -o <out.aln> [-r 0.95] [--type n|p] [--match 18 --mismatch -8 --transition -4\n"
                      "        --gap-open -50 --gap-extend -5 --gap-ends X --xdrop 600] [-w] [--rooted] [--filter] [--check] [-v] [--gpu-index 0,1] [--host-staged]\n";
         if (placement) std::cerr << "       twilight-mi355x -a <backbone.aln[.gz]> -i <new_sequences.fa[.gz]> -o <out.aln> [scoring and filtering flags as above] [--gpu-index 0]\n";
+        if (merging) std::cerr << "       twilight-mi355x -f <directory of alignments (.gz too), searched recursively> -o <out.aln> [scoring flags as above] [-r 0.95] [--type n|p] [-v] [--gpu-index 0]\n"
+                                  "        (every file must hold rows of one length; the output lists the files in sorted order, rows in file order, gaps as '-')\n";
         return 1;
     }
+#ifdef TWL_MERGE
+    if (option.alnMode == msa::MERGE_MSA) {          // one process, one GPU (parseCommandLine refused more)
+        const auto tm = std::chrono::high_resolution_clock::now();
+        const int W = msa::runMerge(option);
+        std::cerr << "Wrote " << option.outFile << " (length " << W << ") in " << std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - tm).count() << " s\n";
+        return 0;
+    }
+#endif
 #ifdef TWL_PLACE
     if (option.alnMode == msa::PLACE_WO_TREE) {      // one process, one GPU (parseCommandLine refused more)
         const auto tp = std::chrono::high_resolution_clock::now();

@@ -1,0 +1,249 @@
+// twilight_amd/csrc/host/merge.cpp -- MERGE_MSA: the alignments of a directory merged into one
+// (reference src/twilight-main.cpp:197-211, `twilight -f DIR -o out.aln`).
+//
+// Every file becomes a node whose profile is its column counts (readAlignment, io.cpp:200-238: alnNum = rows, alnWeight = (float)rows).
+// The tree is a star (readAlignments_and_buildTree, io.cpp:240-299): the nodes sorted by row count, descending, the first one the root,
+// the others its children.  scheduling mode 1 (progressive.cpp:81-95) pairs every child with the root, one pair per level;
+// collectPostOrder (node.cpp:58-71) leaves the LAST child on top of the stack, so the last child is merged first.  Every pair is aligned
+// profile against profile with currentTask 2 (alignment-cpu.cpp:86-130: gapCharScore 0, a failed pair retried until it passes), and no row is
+// touched: what a merge changes is the column map of every file under its two sides (updateAlignment's subtreeAln branch,
+// alignment-helper.cpp:402-423, :449-470).  All of it runs on one device:
+//   all rows of all files -> one store; twl_store_count_columns per file -> its cached profile
+//   per child: twl_level_prepare (two cached sides, no members) / twl_level_align / twl_level_restore, unchanged (include/twl_level.h)
+//   twl_merge_apply           -> the maps of the files under both sides composed with the final path (include/twl_merge.h)
+//   twl_level_commit_from_dp  -> the two cached profiles merged (updateFrequency, alignment-helper.cpp:506-539)
+//   twl_merge_finish          -> every row rewritten through its file's map, once (io.cpp:355-449), read back once and written
+// The output holds the files in sorted order with their rows in file order, which is what the reference's concatenation of its
+// per-file outputs gives for names that sort alike.
+// Two deliberate differences from the reference: a file whose rows differ in length is refused with exit 1 (the reference warns, leaves
+// the row out of the profile and then miswrites it), and there is no temporary directory (-d, -k and -c are not part of this mode: the
+// rows never leave the device between the merges).  A file without rows or without columns is refused as well.
+#include "align_gpu.hpp"
+
+#include "../../../include/twl_merge.h"
+#include "../../../include/twl_place.h"
+
+#include <algorithm>
+#include <cstdio>
+#include <filesystem>
+#include <fstream>
+#include <iostream>
+#include <numeric>
+#include <string>
+#include <vector>
+
+namespace msa {
+
+using progressive::gpu::baseParams;
+using progressive::gpu::die;
+using progressive::gpu::nowMs;
+using progressive::gpu::runsAndConsensus;
+
+namespace {
+
+struct MsaFile { std::string path; std::vector<std::string> names, rows; int32_t L = 0, firstId = 0; };
+
+struct MergeTotals { double count = 0, dp = 0, restore = 0, apply = 0, commit = 0, finish = 0, read = 0, write = 0, kernel = 0; uint64_t cells = 0; int retries = 0; };
+
+void writeRecords(const std::string &outFile, const std::vector<MsaFile> &files, const char *rows, int32_t W)
+{
+    std::ofstream out(outFile, std::ios::binary);
+    if (!out) { fprintf(stderr, "ERROR: Failed to open file: %s\n", outFile.c_str()); exit(1); }
+    size_t k = 0;
+    for (const MsaFile &f : files)
+        for (size_t r = 0; r < f.names.size(); ++r, ++k) {
+            out << '>' << f.names[r] << '\n';
+            if (rows) out.write(rows + k * (size_t)W, W);
+            else out << f.rows[r];
+            out << '\n';
+        }
+    if (!out) { fprintf(stderr, "ERROR: Failed to write file: %s\n", outFile.c_str()); exit(1); }
+}
+
+}  // namespace
+
+int runMerge(Option &option)
+{
+    namespace fs = std::filesystem;
+    using progressive::gpu::ensureInit;
+    using progressive::gpu::selectedDevices;
+    MergeTotals tot;
+
+    // ---- the files: every regular file under the directory, sorted by path (io.cpp:246-261) ----
+    std::vector<std::string> paths;
+    {
+        std::error_code ec;
+        if (!fs::is_directory(option.msaDir, ec)) { std::cerr << "ERROR: " << option.msaDir << " is not a directory.\n"; exit(1); }
+        for (fs::recursive_directory_iterator it(option.msaDir, fs::directory_options::skip_permission_denied, ec), end; !ec && it != end; it.increment(ec))
+            if (it->is_regular_file(ec)) paths.push_back(it->path().string());
+        std::sort(paths.begin(), paths.end());
+    }
+    if (paths.empty()) { std::cerr << "ERROR: no alignment file was found under " << option.msaDir << ".\n"; exit(1); }
+    if (!option.typeGiven) option.type = io::detectType(paths[0]);
+    Params param(option, option.type);
+
+    std::vector<MsaFile> files(paths.size());
+    std::cerr << "====== Alignment Info ======\n";
+    int32_t nRows = 0;
+    for (size_t k = 0; k < paths.size(); ++k) {
+        MsaFile &f = files[k];
+        f.path = paths[k];
+        f.firstId = nRows;
+        io::readRecords(f.path, [&](std::string &name, std::string &seq) { f.names.push_back(name); f.rows.push_back(std::move(seq)); });
+        if (f.rows.empty()) { std::cerr << "ERROR: no rows were read from " << f.path << ".\n"; exit(1); }
+        f.L = (int32_t)f.rows[0].size();
+        for (size_t r = 1; r < f.rows.size(); ++r)
+            if ((int32_t)f.rows[r].size() != f.L) {
+                std::cerr << "ERROR: length of \"" << f.names[r] << "\" (" << f.rows[r].size() << ") does not match in " << f.path << " (" << f.L
+                          << "): the rows of an alignment must all have one length.\n";
+                exit(1);
+            }
+        if (f.L == 0) { std::cerr << "ERROR: the rows of " << f.path << " have no columns.\n"; exit(1); }
+        nRows += (int32_t)f.rows.size();
+        std::cerr << '[' << k + 1 << '/' << paths.size() << "] " << fs::path(f.path).filename().string() << " (Count: " << f.rows.size() << ", Length: " << f.L << ")\n";
+    }
+    const int32_t G = (int32_t)files.size();
+    if (G == 1) {      // nothing to merge: the file comes back as it is
+        writeRecords(option.outFile, files, nullptr, files[0].L);
+        return files[0].L;
+    }
+
+    // ---- one store: the rows of file k are the ids [firstId, firstId + rows); group k = file k, its cached profile has the id k ----
+    ensureInit(&option);
+    const int device = selectedDevices().empty() ? 0 : selectedDevices()[0];
+    std::vector<const char *> rowPtr;
+    std::vector<int32_t> rowLen, groupOff{0}, rowIds((size_t)nRows);
+    for (const MsaFile &f : files) {
+        for (const std::string &r : f.rows) { rowPtr.push_back(r.data()); rowLen.push_back(f.L); }
+        groupOff.push_back((int32_t)rowPtr.size());
+    }
+    std::iota(rowIds.begin(), rowIds.end(), 0);
+    twl_store *st = nullptr;
+    int rc = twl_store_create(device, option.type, nRows, rowPtr.data(), rowLen.data(), &st);
+    if (rc != TWL_OK) die("twl_store_create", rc);
+    for (MsaFile &f : files) for (std::string &r : f.rows) std::string().swap(r);
+    double t = nowMs();
+    for (int32_t k = 0; k < G; ++k)
+        if ((rc = twl_store_count_columns(st, groupOff[k + 1] - groupOff[k], rowIds.data() + groupOff[k], k)) != TWL_OK) die("twl_store_count_columns", rc);
+    tot.count = nowMs() - t;
+    twl_merge *mg = nullptr;
+    if ((rc = twl_merge_create(st, G, groupOff.data(), rowIds.data(), &mg)) != TWL_OK) die("twl_merge_create", rc);
+
+    // ---- the star: most rows first (a stable sort: ties keep the files' order, which the reference's std::sort leaves open) ----
+    std::vector<int32_t> order((size_t)G);
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return files[a].names.size() > files[b].names.size(); });
+    const int32_t root = order[0];
+    int32_t rootLen = files[root].L, rootNum = (int32_t)files[root].names.size();
+    float rootWeight = (float)rootNum;
+    std::vector<int32_t> rootGroups{root};
+
+    const twl_params tp = baseParams(param);
+    twl_params tz = tp;
+    tz.gap_char = 0;                                       // alignment-cpu.cpp:88 (currentTask 2)
+    const bool removal = !(option.gappyVertical == 1.0f);
+    static const char bases[] = {'A', 'C', 'G', 'T', 'N'};
+    static const char acids[] = {'A', 'C', 'D', 'E', 'F', 'G', 'H', 'I', 'K', 'L', 'M', 'N', 'P', 'Q', 'R', 'S', 'T', 'V', 'W', 'Y', 'X'};
+    const char *letters = (option.type == 'n') ? bases : acids;
+
+    // ---- one level per child, the last child first ----
+    for (int32_t at = G - 1; at >= 1; --at) {
+        const int32_t child = order[at];
+        const int32_t qLen = files[child].L, qNum = (int32_t)files[child].names.size();
+        const float qWeight = (float)qNum;
+        const int32_t maxLen = std::max(rootLen, qLen);
+        const twl_side sides[2] = {twl_side{0, 0, rootLen, rootNum, rootWeight, root, -1, 0}, twl_side{0, 0, qLen, qNum, qWeight, child, -1, 0}};
+        int32_t lenOut[2] = {0, 0}, alnLen = 0;
+        int16_t err = 0;
+        double t0 = nowMs();
+        if ((rc = twl_level_prepare(st, &tp, option.gappyVertical, 1, sides, nullptr, nullptr, maxLen, lenOut, nullptr)) != TWL_OK) die("twl_level_prepare", rc);
+        twl_stats ss{};
+        auto runOnce = [&](const twl_params &prm) {
+            if ((rc = twl_level_align(st, &prm, nullptr, nullptr, &alnLen, &err)) != TWL_OK) die("twl_level_align", rc);
+            if (twl_get_stats(device, &ss) == TWL_OK) { tot.cells += ss.band_cells; tot.kernel += ss.kernel_ms; }
+            return err;
+        };
+        runOnce(tz);
+        {   // alignment-cpu.cpp:95-128 with currentTask 2: retried until errorType 0
+            twl_params tr = tz;
+            progressive::retryUntilPassed(tr, err, std::min(lenOut[0], lenOut[1]), [&](const twl_params &grown) {
+                ++tot.retries;
+                if (option.printDetail) std::cout << "Retry alignment " << fs::path(files[child].path).filename().string() << "\txdrop " << grown.xdrop << " flen " << grown.flen << '\n';
+                return runOnce(grown);
+            });
+        }
+        tot.dp += nowMs() - t0;
+
+        // gappy columns back (alignment-helper.cpp:324-375) when a side lost a column; otherwise the path is final as the DP left it
+        t0 = nowMs();
+        const int32_t stride = rootLen + qLen;
+        uint8_t fromDp = 1;
+        int32_t pathLen = alnLen;
+        if (lenOut[0] < rootLen || lenOut[1] < qLen) {
+            const int32_t sel = 0;
+            int32_t fin = -1;
+            if ((rc = twl_level_restore(st, &tp, 1, &sel, stride, &fin)) != TWL_OK) die("twl_level_restore", rc);
+            if (fin > 0) pathLen = fin;
+            else {      // a two-sided run too large for the device: restored on the host, into the level's path buffer
+                const size_t sl = (size_t)maxLen;
+                std::vector<uint8_t> info(2 * sl);
+                std::vector<int8_t> raw(2 * sl);
+                if ((rc = twl_level_read_colinfo_many(st, 1, &sel, info.data())) != TWL_OK) die("twl_level_read_colinfo_many", rc);
+                if ((rc = twl_level_read_paths(st, 1, &sel, &alnLen, raw.data(), (int32_t)(2 * sl))) != TWL_OK) die("twl_level_read_paths", rc);
+                std::pair<IntPairVec, IntPairVec> gappy;
+                stringPair cons;
+                runsAndConsensus(&info[0], rootLen, removal, letters, gappy.first, cons.first);
+                runsAndConsensus(&info[sl], qLen, removal, letters, gappy.second, cons.second);
+                alnPath path(raw.data(), raw.data() + alnLen), full;
+                int alnRef = 0, alnQry = 0;
+                for (auto a : path) { if (a != 1) ++alnRef; if (a != 2) ++alnQry; }
+                alignment_helper::addGappyColumnsBack(path, full, gappy, param, {alnRef, alnQry}, cons);
+                if ((int32_t)full.size() > stride) { std::cerr << "ERROR: path longer than both sides together.\n"; exit(1); }
+                if ((rc = twl_level_write_final(st, 0, full.data(), (int32_t)full.size())) != TWL_OK) die("twl_level_write_final", rc);
+                pathLen = (int32_t)full.size();
+            }
+            fromDp = 2;
+        }
+        tot.restore += nowMs() - t0;
+
+        // the maps of the files under both sides, then the two profiles (updateAlignment / updateFrequency, alignment-cpu.cpp:169-170)
+        t0 = nowMs();
+        const int32_t refOff[2] = {0, (int32_t)rootGroups.size()}, qryOff[2] = {0, 1};
+        if ((rc = twl_merge_apply(mg, st, 1, refOff, rootGroups.data(), qryOff, &child, nullptr, &pathLen, stride, &fromDp)) != TWL_OK) die("twl_merge_apply", rc);
+        tot.apply += nowMs() - t0;
+        t0 = nowMs();
+        if ((rc = twl_level_commit_from_dp(st, nullptr, &pathLen, stride, &fromDp)) != TWL_OK) die("twl_level_commit_from_dp", rc);
+        tot.commit += nowMs() - t0;
+        // alignment-helper.cpp:474-477
+        rootNum += qNum;
+        rootLen = pathLen;
+        rootWeight += qWeight;
+        rootGroups.push_back(child);
+        if (option.printDetail)
+            std::cerr << "Merged " << fs::path(files[child].path).filename().string() << " (" << qNum << " rows, " << qLen << " columns): " << rootNum << " rows, " << rootLen << " columns\n";
+    }
+
+    // ---- every row through its file's map, once; one read-back; output ----
+    int32_t W = 0;
+    t = nowMs();
+    if ((rc = twl_merge_finish(mg, &W)) != TWL_OK) die("twl_merge_finish", rc);
+    tot.finish = nowMs() - t;
+    t = nowMs();
+    std::vector<int32_t> outLen((size_t)nRows);
+    std::vector<char> rows((size_t)nRows * (size_t)W + 1);
+    if ((rc = twl_store_read_rows_of(st, nRows, rowIds.data(), rows.data(), outLen.data())) != TWL_OK) die("twl_store_read_rows_of", rc);
+    tot.read = nowMs() - t;
+    twl_merge_destroy(mg);
+    twl_store_destroy(st);
+    t = nowMs();
+    writeRecords(option.outFile, files, rows.data(), W);
+    tot.write = nowMs() - t;
+    std::cerr << "Merged " << G << " alignments (" << nRows << " rows): final alignment length " << W << ", " << tot.retries << " retried DP run(s)\n";
+    if (option.printDetail)
+        fprintf(stderr, "Merge phases (ms): count %.3f, prepare+DP %.3f, restore %.3f, apply %.3f, commit %.3f, finish %.3f, read-back %.3f, write %.3f; "
+                        "DP kernel %.3f ms, %llu band cells\n", tot.count, tot.dp, tot.restore, tot.apply, tot.commit, tot.finish, tot.read, tot.write, tot.kernel,
+                (unsigned long long)tot.cells);
+    return W;
+}
+
+}  // namespace msa

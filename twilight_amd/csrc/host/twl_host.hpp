@@ -130,6 +130,8 @@ struct Option {
     bool hostStaged = false;     // --host-staged: build profiles on the host and stage them per level (default: device-resident rows)
     std::string backboneAlnFile; // -a / --alignment: the existing alignment new sequences are placed into (alnMode PLACE_WO_TREE)
     int testPlaceChunk = 0;      // --test-place-chunk n: placement aligns at most n sequences per level (default: sized to device memory)
+    std::string msaDir;          // -f / --files: a directory of alignments to merge into one (alnMode MERGE_MSA)
+    bool typeGiven = false;      // --type was given (a merge detects the type from its first file otherwise)
     // scoring flags (consumed by Params)
     float match = 18, mismatch = -8, transition = -4, gapOpen = -50, gapExtend = -5, xdrop = 600;
     bool hasGapEnds = false;
@@ -301,9 +303,13 @@ void downloadRows(SequenceDB *database, Tree *T);
 int runDefaultAlignment(Option &option, alnFunction kernel, alnFunction deferredKernel, bool writeOutput = true,
                         const std::function<void(SequenceDB *)> &atEnd = nullptr, const std::function<void(SequenceDB *)> &beforeAlign = nullptr);
 // allowPlacement: the binary carries the placement mode (twilight-mi355x): -a/--alignment with -i/-o and no -t selects PLACE_WO_TREE
-bool parseCommandLine(int argc, char **argv, Option &option, bool allowPlacement = false);
+// allowMerge: the binary carries the merge mode as well: -f/--files with -o and none of -t, -i, -a selects MERGE_MSA
+bool parseCommandLine(int argc, char **argv, Option &option, bool allowPlacement = false, bool allowMerge = false);
 // PLACE_WO_TREE (place.cpp, libtwl_host.so): the sequences of option.seqFile placed into the alignment option.backboneAlnFile, written to
 // option.outFile.  Returns the final alignment length.
 int runPlacement(Option &option);
+// MERGE_MSA (merge.cpp, libtwl_host.so): the alignments found under option.msaDir merged into one, written to option.outFile.  Returns the
+// final alignment length.
+int runMerge(Option &option);
 
 }  // namespace msa

@@ -43,7 +43,7 @@ struct Call {
     int32_t stride = 64;
     std::vector<uint8_t> fromDp;
     bool havePaths = true, finished = false;
-    MergeLevelView lv;
+    PathLevelView lv;
 };
 static const char *apply(const MergeGroups &g, const Call &c, MergeApplyPlan &p)
 {
@@ -64,7 +64,7 @@ static void apply_kats()
     CHECK("apply_plan_rank_tables", p.rOff == std::vector<int64_t>({0}) && p.qOff == std::vector<int64_t>({10}) && p.rankInts == 17);
     CHECK("apply_plan_jobs", p.jobs.size() == 2 && p.jobs[0].pos_off == 0 && p.jobs[0].tab_off == 0 && p.jobs[0].L == 10 && p.jobs[0].tab_len == 10 &&
                              p.jobs[1].pos_off == 10 && p.jobs[1].tab_off == 10 && p.jobs[1].L == 7 && p.jobs[1].tab_len == 7 && p.maxL == 10);
-    CHECK("apply_plan_host_row", p.which == std::vector<uint8_t>({0}) && p.hostRows == V({0}) && p.srcOff == std::vector<int64_t>({0}));
+    CHECK("apply_plan_host_row", p.src.which == std::vector<uint8_t>({0}) && p.src.hostRows == V({0}) && p.src.srcOff == std::vector<int64_t>({0}));
     // the shape of a path is decided on what the rank kernel counted
     const int32_t good[3] = {10, 7, 0}, shortRef[3] = {9, 7, 0}, longQry[3] = {10, 8, 0}, badCode[3] = {10, 7, 1};
     CHECK("counts_accept_exact_cover", check_merge_counts(p, good) == nullptr);
@@ -94,7 +94,7 @@ static void apply_kats()
     CHECK("apply_skipped_pair_does_not_count", apply(g, twoPairs, p) == nullptr && p.pair == V({0}));
     twoPairs.qryG = {1, 3}; twoPairs.plen = {12, 15};
     CHECK("apply_accepts_two_pairs", apply(g, twoPairs, p) == nullptr && p.pair == V({0, 1}) && p.rOff == std::vector<int64_t>({0, 17}) && p.qOff == std::vector<int64_t>({10, 29}) &&
-                                     p.rankInts == 39 && p.srcOff == std::vector<int64_t>({0, 64}) && p.maxL == 12);
+                                     p.rankInts == 39 && p.src.srcOff == std::vector<int64_t>({0, 64}) && p.maxL == 12);
     c = one; c.refG = {4};
     CHECK("apply_rejects_group_4_of_4", is(apply(g, c, p), "group id out of range"));
     c = one; c.qryG = {-1};
@@ -119,7 +119,7 @@ static void apply_kats()
     CHECK("apply_rejects_after_finish", is(apply(g, c, p), "twl_merge_apply after twl_merge_finish"));
     c = one; c.plen = {0};
     CHECK("apply_all_skipped_is_empty", apply(g, c, p) == nullptr && p.pair.empty() && p.jobs.empty());
-    CHECK("apply_no_pairs", check_merge_apply(g, false, 0, nullptr, nullptr, nullptr, nullptr, false, nullptr, 0, nullptr, MergeLevelView{}, p) == nullptr);
+    CHECK("apply_no_pairs", check_merge_apply(g, false, 0, nullptr, nullptr, nullptr, nullptr, false, nullptr, 0, nullptr, PathLevelView{}, p) == nullptr);
 
     // paths that stay on the device
     c = one; c.fromDp = {1};
@@ -129,7 +129,7 @@ static void apply_kats()
     c.lv.n_pairs = 1; c.lv.dp_stride = 24;
     CHECK("apply_from_dp_1_needs_a_dp_output", is(apply(g, c, p), "from_dp 1 without a DP output of that length"));
     c.lv.has_dp = true;
-    CHECK("apply_accepts_from_dp_1", apply(g, c, p) == nullptr && p.which == std::vector<uint8_t>({1}) && p.hostRows.empty() && p.srcOff == std::vector<int64_t>({0}));
+    CHECK("apply_accepts_from_dp_1", apply(g, c, p) == nullptr && p.src.which == std::vector<uint8_t>({1}) && p.src.hostRows.empty() && p.src.srcOff == std::vector<int64_t>({0}));
     c.lv.dp_stride = 11;
     CHECK("apply_from_dp_1_longer_than_the_dp_row", is(apply(g, c, p), "from_dp 1 without a DP output of that length"));
     c.lv.dp_stride = 24; c.fromDp = {2};
@@ -137,13 +137,13 @@ static void apply_kats()
     c.lv.staged_stride = 32;
     CHECK("apply_from_dp_2_needs_the_restore_pitch", is(apply(g, c, p), "from_dp 2: twl_level_restore first, with this row pitch"));
     c.lv.staged_stride = 64;
-    CHECK("apply_accepts_from_dp_2", apply(g, c, p) == nullptr && p.which == std::vector<uint8_t>({2}));
+    CHECK("apply_accepts_from_dp_2", apply(g, c, p) == nullptr && p.src.which == std::vector<uint8_t>({2}));
     c.fromDp = {3};
     CHECK("apply_rejects_from_dp_3", is(apply(g, c, p), "from_dp must be 0, 1 or 2"));
     // the second pair of a level reads its own row of the level's buffers
     Call lvl = twoPairs;
     lvl.fromDp = {2, 1}; lvl.lv.prepared = true; lvl.lv.n_pairs = 2; lvl.lv.dp_stride = 24; lvl.lv.has_dp = true; lvl.lv.staged_stride = 64;
-    CHECK("apply_level_rows", apply(g, lvl, p) == nullptr && p.srcOff == std::vector<int64_t>({0, 24}) && p.which == std::vector<uint8_t>({2, 1}));
+    CHECK("apply_level_rows", apply(g, lvl, p) == nullptr && p.src.srcOff == std::vector<int64_t>({0, 24}) && p.src.which == std::vector<uint8_t>({2, 1}));
 }
 
 static void finish_kats()

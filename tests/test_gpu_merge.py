@@ -302,3 +302,48 @@ def test_cli_single_file_is_written_back(gpu, tmp_path):
     r = _cli("-f", str(d), "-o", str(out))
     assert r.returncode == 0, r.stderr
     assert out.read_bytes() == data
+
+
+def _files_with_one_gappy_block(rng, n_rows=24, flank=25, block=150):
+    """Two nucleotide alignments of n_rows rows x (2 * flank + block) columns over one ancestor: in each, `block` columns at column `flank`
+    in which exactly one row has letters and the others have gaps."""
+    anc = rng.choice(list(b"ACGT"), 2 * flank).astype(np.uint8)
+    files = []
+    for k in range(2):
+        recs = []
+        for r in range(n_rows):
+            mid = rng.choice(list(b"ACGT"), block).astype(np.uint8) if r == k else np.full(block, ord("-"), np.uint8)
+            recs.append((b"f%d_r%d" % (k, r), np.concatenate([anc[:flank], mid, anc[flank:]]).tobytes()))
+        files.append(recs)
+    return files
+
+
+def test_cli_two_sided_run_too_large_for_the_device_is_restored_on_the_host(gpu, tmp_path):
+    """Both profiles lose a run of 150 columns at one step of the path (23 of 24 rows have gaps there: 23/24 > -r 0.95, compared with > in
+    level_oracle.gappy_mask): the 151 x 151 alignment of the two runs does not fit the restore kernel's scratch (NW_CELLS), the device hands
+    the pair back and the final path is made on the host -- the final-path step the tree path shares with -f and -a.  -v must say so and
+    the output must be the oracle's, byte for byte.  (Placement has no such test: its query side is one sequence, which never loses a
+    column, so no step of a placement's path has a run on both sides and nothing is handed back.)"""
+    import level_cases as LC
+    import level_oracle as LO
+
+    files = _files_with_one_gappy_block(np.random.default_rng(24))
+    # on the CPU first: both sides lose one run of 150 columns, at the same column, and the two together are too big for the device
+    runs = []
+    for recs in files:
+        prof = MO.PO.backbone_profile([r for _, r in recs], "n")
+        side = LO.profile_from_cache(prof, MO.F(len(recs)), len(recs))
+        runs.append([tuple(int(x) for x in run) for run in LO.prepare_side(side, len(recs), 0.95, -50.0, -5.0, "n")[2]])
+    assert runs[0] == runs[1] == [(25, 150)], runs
+    assert LC.too_big(runs[0][0][1], runs[1][0][1])
+    want, W, _, _ = MO.merge(files, "n")
+    d = tmp_path / "in"
+    d.mkdir()
+    for name, recs in zip(("a.aln", "b.aln"), files):
+        (d / name).write_bytes(MO.to_bytes(recs))
+    out = tmp_path / "out.aln"
+    r = _cli("-f", str(d), "-o", str(out), "-v")
+    assert r.returncode == 0, r.stderr
+    handed = sum(int(l.split("restored on the host ")[1].split(";")[0]) for l in r.stderr.splitlines() if "restored on the host" in l)
+    assert handed >= 1, r.stderr
+    assert out.read_bytes() == MO.to_bytes(want) and len(MO.PO.read_fasta(str(out))[0][1]) == W

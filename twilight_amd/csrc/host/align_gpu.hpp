@@ -6,6 +6,7 @@
 #include "../../../include/twl_level.h"
 
 #include <chrono>
+#include <functional>
 
 namespace msa {
 namespace progressive {
@@ -49,6 +50,31 @@ const std::vector<int> &selectedDevices();
 twl_params baseParams(Params &param);          // == Talco_xdrop::Params(msa::Params&), TALCO-XDrop.cpp:36-53
 // Consensus string and removed-column runs of one side from the column info of twl_level_prepare (letters: "ACGTN" / the 20 acids + 'X').
 void runsAndConsensus(const uint8_t *info, int len, bool removal, const char *letters, IntPairVec &runs, std::string &cons);
+const char *consensusLetters(char type);       // the letter of a column-info code, for runsAndConsensus
+// Column info of one pair for addGappyColumnsBack: removed-column runs and consensus of the two sides.
+struct ColumnInfo { std::pair<IntPairVec, IntPairVec> gappy; stringPair consensus; };
+// Gappy columns back on the host for one pair (alignment-helper.cpp:324-375): `full` from its DP path.  Returns the codes != 1 and != 2 of
+// `full`; a path longer than the row pitch of the final paths ends the run.
+IntPair restoreOnHost(alnPath &dp, ColumnInfo &cols, Params &param, int pathStride, alnPath &full);
+
+// The n pairs of a store's prepared and aligned level: sideLen / lenOut [2n] = length of every side before / after gappy-column removal,
+// alnLen / err [n] = what the DP left, stride / pathStride = row pitch of the level (its longest side) and of its final paths.
+struct AlignedLevel { int32_t n; const int32_t *sideLen, *lenOut, *alnLen; const int16_t *err; int32_t stride, pathStride; };
+// (rare: a two-sided run too large for the device) the pairs twl_level_restore handed back: their column info and DP paths (dpLen codes) come
+// to the host, the host puts the columns back and writes the result into the level's path buffer.  Returns the final length of each;
+// post(pair, codes != 1, codes != 2), if given, sees every restored path.
+std::vector<int32_t> restoreHandedBack(twl_store *st, Params &param, const Option &option, const AlignedLevel &lv, const std::vector<int32_t> &pairs,
+                                       const std::vector<int32_t> &dpLen, const std::function<void(int, int, int)> &post = nullptr);
+// The final path of every pair with err == 0, all in HBM: as the DP left it (fromDp 1) when no column was removed, otherwise with its gappy
+// columns back (fromDp 2: twl_level_restore, or restoreHandedBack for the pairs it hands back).
+struct FinalPaths { std::vector<uint8_t> fromDp; std::vector<int32_t> pathLen; int restoredOnHost = 0; };
+FinalPaths finalPathsOfLevel(twl_store *st, const twl_params &tp, Params &param, const Option &option, const AlignedLevel &lv);
+// twl_level_align over the store's prepared level, the device's stats added to `tot`; with retryWhat, the level's ONE pair is retried until it
+// passes (alignment-cpu.cpp:95-128 with currentTask != 0; -v: "Retry <retryWhat> ...").  knownErr: that pair's DP has run already and ended
+// with *knownErr.  minLen: its shorter side after gappy-column removal.
+struct DpTotals { double kernel = 0; uint64_t cells = 0; int retries = 0; };
+void alignWithRetry(twl_store *st, int device, const twl_params &prm, const Option &option, const std::string *retryWhat, const int16_t *knownErr, int32_t minLen,
+                    int32_t *alnLen, int16_t *err, DpTotals &tot);
 inline double nowMs() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 }  // namespace gpu

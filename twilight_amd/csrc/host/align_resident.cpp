@@ -142,12 +142,6 @@ void materialise(Tree *T, SequenceDB *db, Option *option)
     if (option->printDetail) std::cerr << "Rows back on the host in " << nowMs() - t0 << " ms\n";
 }
 
-// Column info of one pair for addGappyColumnsBack: removed-column runs and consensus of the two sides.
-struct ColumnInfo {
-    std::pair<IntPairVec, IntPairVec> gappy;
-    stringPair consensus;
-};
-
 // How the paths of a level travel, from the shard and the replica count.  inPlace and devX hold for ONE replica only (nd == 1 in every
 // term): twl_level_restore, the pairs it hands back and the HBM-to-HBM exchange never meet a second replica thread.
 struct PathRoute { bool procs, devX, inPlace; };
@@ -163,9 +157,6 @@ PathRoute routeOf(const Shard &sh, int nd)
     r.inPlace = (nd == 1 && ((!r.procs && !sh.exchange && !sh.rccl) || r.devX));
     return r;
 }
-
-const char kBases[] = {'A', 'C', 'G', 'T', 'N'};
-const char kAcids[] = {'A', 'C', 'D', 'E', 'F', 'G', 'H', 'I', 'K', 'L', 'M', 'N', 'P', 'Q', 'R', 'S', 'T', 'V', 'W', 'Y', 'X'};
 
 // One level.  The steps below fill it in turn on the calling thread (each group of members names its step); the replica threads of
 // alignShare get it const.  Steps that change the run or the nodes take RunCtx / NodePairVec as an argument of their own.
@@ -197,7 +188,7 @@ struct Level {
     int meBase = 0;                               // replica d of this process aligns the pairs of owner meBase + d
     Level(const RunCtx &c, const NodePairVec &nv, SequenceDB *db, Option *o, Params &p)
         : ctx(c), nodes(nv), database(db), option(o), param(p), task(db->currentTask), n((int)nv.size()), nd((int)c.stores.size()),
-          letters(o->type == 'n' ? kBases : kAcids), removal(!(o->gappyVertical == 1.0)), route(routeOf(c.shard, nd)), tp(baseParams(p)), tz(tp)
+          letters(consensusLetters(o->type)), removal(!(o->gappyVertical == 1.0)), route(routeOf(c.shard, nd)), tp(baseParams(p)), tz(tp)
     {
         tz.gap_char = 0;
     }
@@ -473,41 +464,28 @@ void mergeShares(const std::vector<ReplicaShare> &shares, RunCtx &ctx, LevelReco
     ctx.totals.nominal_cells += shares[0].nominalCells;
 }
 
-// gappy columns back on the host for one pair (alignment-helper.cpp:324-375)
-void restoreOnHost(const Level &lv, PairRows &rows, int i, alnPath &full)
+// what restoreOnHost made of pair i must cover both of its sides
+void postCheck(const Level &lv, int i, int alnRef, int alnQry)
 {
     const PairShape &s = lv.ps[i];
-    int alnRef = 0, alnQry = 0;
-    for (auto a : rows.paths[i]) { if (a != 1) ++alnRef; if (a != 2) ++alnQry; }
-    alignment_helper::addGappyColumnsBack(rows.paths[i], full, rows.cols[i].gappy, lv.param, {alnRef, alnQry}, rows.cols[i].consensus);
-    alnRef = alnQry = 0;
-    for (auto a : full) { if (a != 1) ++alnRef; if (a != 2) ++alnQry; }
     if (alnRef != s.refLen) std::cout << "R: Post " << lv.nodes[i].first->identifier << "(" << alnRef << "/" << s.refLen << ")\n";
     if (alnQry != s.qryLen) std::cout << "Q: Post " << lv.nodes[i].second->identifier << "(" << alnQry << "/" << s.qryLen << ")\n";
-    if ((int)full.size() > lv.pathStride) { std::cerr << "ERROR: path longer than both profiles together.\n"; exit(1); }
 }
 
-// (rare: a two-sided run too large for the device) the pairs the device handed back: their column info and DP paths come to the host,
-// the host puts the columns back and its result joins the others in HBM.  In-place mode only, hence one replica: share 0.
+// The pairs the device handed back: the host's result joins the others in HBM.  In-place mode only, hence one replica: share 0.
 void joinHandedBack(const Level &lv, const ReplicaShare &share, PairRows &rows)
 {
     const std::vector<int32_t> &fetch = share.handedBack;
     if (fetch.empty()) return;
     if (!lv.route.inPlace) { std::cerr << "ERROR: pairs handed back to the host outside the in-place mode.\n"; exit(1); }
-    const size_t pitch = (size_t)2 * lv.stride;
-    fetchColumnInfo(lv, std::vector<int>(fetch.begin(), fetch.end()), false, rows.cols);
-    int8_t *blk = reinterpret_cast<int8_t *>(g_alnStage[0].get(fetch.size() * pitch));
-    int rc = twl_level_read_paths(firstStore(lv.ctx), (int32_t)fetch.size(), fetch.data(), share.handedBackLen.data(), blk, (int32_t)pitch);
-    if (rc != TWL_OK) die("twl_level_read_paths", rc);
+    std::vector<int32_t> sideLen(2 * (size_t)lv.n);
+    for (int i = 0; i < lv.n; ++i) { sideLen[2 * i] = lv.ps[i].refLen; sideLen[2 * i + 1] = lv.ps[i].qryLen; }
+    const AlignedLevel al{lv.n, sideLen.data(), nullptr, nullptr, nullptr, lv.stride, lv.pathStride};
+    const std::vector<int32_t> fin = restoreHandedBack(firstStore(lv.ctx), lv.param, *lv.option, al, fetch, share.handedBackLen,
+                                                       [&](int i, int alnRef, int alnQry) { postCheck(lv, i, alnRef, alnQry); });
     for (size_t t = 0; t < fetch.size(); ++t) {
-        const int i = fetch[t];
-        rows.paths[i].assign(&blk[t * pitch], &blk[t * pitch] + share.handedBackLen[t]);
-        if (rows.errs[i] != 0 || rows.paths[i].empty()) continue;
-        alnPath full;
-        restoreOnHost(lv, rows, i, full);
-        if ((rc = twl_level_write_final(firstStore(lv.ctx), i, full.data(), (int32_t)full.size())) != TWL_OK) die("twl_level_write_final", rc);
-        rows.fromDp[i] = 2; rows.dpLen[i] = (int32_t)full.size();
-        rows.paths[i].clear();
+        rows.fromDp[fetch[t]] = 2; rows.dpLen[fetch[t]] = fin[t];
+        rows.paths[fetch[t]].clear();
     }
 }
 
@@ -548,7 +526,7 @@ int8_t *finalPathsOnHost(const Level &lv, PairRows &rows, std::vector<int32_t> &
 #pragma omp parallel for schedule(dynamic, 1) if (onHost.size() > 1)
     for (int t = 0; t < (int)onHost.size(); ++t) {
         const int i = onHost[t];
-        const ColumnInfo &c = rows.cols[i];
+        ColumnInfo &c = rows.cols[i];
         if (c.gappy.first.empty() && c.gappy.second.empty()) {      // nothing was removed: the DP path is the final path (addGappyColumnsBack would copy it)
             if ((int)rows.paths[i].size() > pathStride) { std::cerr << "ERROR: path longer than both profiles together.\n"; exit(1); }
             std::copy(rows.paths[i].begin(), rows.paths[i].end(), &finalPaths[(size_t)i * pathStride]);
@@ -556,7 +534,8 @@ int8_t *finalPathsOnHost(const Level &lv, PairRows &rows, std::vector<int32_t> &
             continue;
         }
         alnPath full;
-        restoreOnHost(lv, rows, i, full);
+        const IntPair covers = restoreOnHost(rows.paths[i], c, lv.param, pathStride, full);
+        postCheck(lv, i, covers.first, covers.second);
         std::copy(full.begin(), full.end(), &finalPaths[(size_t)i * pathStride]);
         finalLen[i] = (int32_t)full.size();
     }
@@ -581,6 +560,96 @@ void commitAndBookkeep(const Level &lv, RunCtx &ctx, NodePairVec &nodes, const i
 }
 
 }  // namespace
+
+const char *consensusLetters(char type)
+{
+    static const char bases[] = {'A', 'C', 'G', 'T', 'N'};
+    static const char acids[] = {'A', 'C', 'D', 'E', 'F', 'G', 'H', 'I', 'K', 'L', 'M', 'N', 'P', 'Q', 'R', 'S', 'T', 'V', 'W', 'Y', 'X'};
+    return type == 'n' ? bases : acids;
+}
+
+IntPair restoreOnHost(alnPath &dp, ColumnInfo &cols, Params &param, int pathStride, alnPath &full)
+{
+    auto covers = [](const alnPath &p) { IntPair c{0, 0}; for (auto a : p) { c.first += a != 1; c.second += a != 2; } return c; };
+    alignment_helper::addGappyColumnsBack(dp, full, cols.gappy, param, covers(dp), cols.consensus);
+    if ((int)full.size() > pathStride) { std::cerr << "ERROR: path longer than both profiles together.\n"; exit(1); }
+    return covers(full);
+}
+
+std::vector<int32_t> restoreHandedBack(twl_store *st, Params &param, const Option &option, const AlignedLevel &lv, const std::vector<int32_t> &pairs,
+                                       const std::vector<int32_t> &dpLen, const std::function<void(int, int, int)> &post)
+{
+    const size_t sl = (size_t)lv.stride, m = pairs.size();
+    const bool removal = !(option.gappyVertical == 1.0f);
+    const char *letters = consensusLetters(option.type);
+    std::vector<uint8_t> info(m * 2 * sl);
+    std::vector<int8_t> raw(m * 2 * sl);
+    int rc = twl_level_read_colinfo_many(st, (int32_t)m, pairs.data(), info.data());
+    if (rc != TWL_OK) die("twl_level_read_colinfo_many", rc);
+    if ((rc = twl_level_read_paths(st, (int32_t)m, pairs.data(), dpLen.data(), raw.data(), (int32_t)(2 * sl))) != TWL_OK) die("twl_level_read_paths", rc);
+    std::vector<int32_t> fin(m);
+    for (size_t k = 0; k < m; ++k) {
+        const int32_t i = pairs[k];
+        ColumnInfo c;
+        runsAndConsensus(&info[2 * k * sl], lv.sideLen[2 * i], removal, letters, c.gappy.first, c.consensus.first);
+        runsAndConsensus(&info[(2 * k + 1) * sl], lv.sideLen[2 * i + 1], removal, letters, c.gappy.second, c.consensus.second);
+        alnPath dp(&raw[2 * k * sl], &raw[2 * k * sl] + dpLen[k]), full;
+        const IntPair covers = restoreOnHost(dp, c, param, lv.pathStride, full);
+        if (post) post(i, covers.first, covers.second);
+        if ((rc = twl_level_write_final(st, i, full.data(), (int32_t)full.size())) != TWL_OK) die("twl_level_write_final", rc);
+        fin[k] = (int32_t)full.size();
+    }
+    return fin;
+}
+
+FinalPaths finalPathsOfLevel(twl_store *st, const twl_params &tp, Params &param, const Option &option, const AlignedLevel &lv)
+{
+    FinalPaths f;
+    f.fromDp.assign((size_t)lv.n, 0);
+    f.pathLen.assign((size_t)lv.n, 0);
+    std::vector<int32_t> sel;                     // the pairs that lost a column; the others are final as the DP left them
+    for (int32_t i = 0; i < lv.n; ++i) {
+        if (lv.err[i] != 0) continue;
+        f.pathLen[i] = lv.alnLen[i];
+        f.fromDp[i] = 1;
+        if (lv.lenOut[2 * i] < lv.sideLen[2 * i] || lv.lenOut[2 * i + 1] < lv.sideLen[2 * i + 1]) sel.push_back(i);
+    }
+    if (sel.empty()) return f;
+    std::vector<int32_t> fin(sel.size(), -1), host, hostLen;
+    const int rc = twl_level_restore(st, &tp, (int32_t)sel.size(), sel.data(), lv.pathStride, fin.data());
+    if (rc != TWL_OK) die("twl_level_restore", rc);
+    for (size_t k = 0; k < sel.size(); ++k) {
+        f.fromDp[sel[k]] = 2;
+        if (fin[k] > 0) f.pathLen[sel[k]] = fin[k];
+        else { host.push_back(sel[k]); hostLen.push_back(lv.alnLen[sel[k]]); }
+    }
+    if (!host.empty()) {
+        const std::vector<int32_t> full = restoreHandedBack(st, param, option, lv, host, hostLen);
+        for (size_t k = 0; k < host.size(); ++k) f.pathLen[host[k]] = full[k];
+        f.restoredOnHost = (int)host.size();
+    }
+    return f;
+}
+
+void alignWithRetry(twl_store *st, int device, const twl_params &prm, const Option &option, const std::string *retryWhat, const int16_t *knownErr, int32_t minLen,
+                    int32_t *alnLen, int16_t *err, DpTotals &tot)
+{
+    auto runOnce = [&](const twl_params &p) {
+        const int rc = twl_level_align(st, &p, nullptr, nullptr, alnLen, err);
+        if (rc != TWL_OK) die("twl_level_align", rc);
+        twl_stats ss{};
+        if (twl_get_stats(device, &ss) == TWL_OK) { tot.cells += ss.band_cells; tot.kernel += ss.kernel_ms; }
+        return err[0];
+    };
+    const int16_t first = knownErr ? *knownErr : runOnce(prm);
+    if (!retryWhat) return;
+    twl_params tr = prm;
+    retryUntilPassed(tr, first, minLen, [&](const twl_params &grown) {
+        ++tot.retries;
+        if (option.printDetail) std::cout << "Retry " << *retryWhat << "\txdrop " << grown.xdrop << " flen " << grown.flen << '\n';
+        return runOnce(grown);
+    });
+}
 
 void runsAndConsensus(const uint8_t *info, int len, bool removal, const char *letters, IntPairVec &runs, std::string &cons)
 {

@@ -26,7 +26,6 @@
 #include <algorithm>
 #include <cstdio>
 #include <filesystem>
-#include <fstream>
 #include <iostream>
 #include <numeric>
 #include <string>
@@ -37,27 +36,26 @@ namespace msa {
 using progressive::gpu::baseParams;
 using progressive::gpu::die;
 using progressive::gpu::nowMs;
-using progressive::gpu::runsAndConsensus;
+using progressive::gpu::alignWithRetry;
+using progressive::gpu::finalPathsOfLevel;
 
 namespace {
 
 struct MsaFile { std::string path; std::vector<std::string> names, rows; int32_t L = 0, firstId = 0; };
 
-struct MergeTotals { double count = 0, dp = 0, restore = 0, apply = 0, commit = 0, finish = 0, read = 0, write = 0, kernel = 0; uint64_t cells = 0; int retries = 0; };
+struct MergeTotals { double count = 0, dp = 0, restore = 0, apply = 0, commit = 0, finish = 0, read = 0, write = 0; progressive::gpu::DpTotals run; int restoredOnHost = 0; };
 
+// the files' records in order; rows: all rows at W columns back to back, or nullptr for the rows as they were read
 void writeRecords(const std::string &outFile, const std::vector<MsaFile> &files, const char *rows, int32_t W)
 {
-    std::ofstream out(outFile, std::ios::binary);
-    if (!out) { fprintf(stderr, "ERROR: Failed to open file: %s\n", outFile.c_str()); exit(1); }
-    size_t k = 0;
+    std::vector<const std::string *> names;
+    std::vector<const char *> rowAt;
     for (const MsaFile &f : files)
-        for (size_t r = 0; r < f.names.size(); ++r, ++k) {
-            out << '>' << f.names[r] << '\n';
-            if (rows) out.write(rows + k * (size_t)W, W);
-            else out << f.rows[r];
-            out << '\n';
+        for (size_t r = 0; r < f.names.size(); ++r) {
+            rowAt.push_back(rows ? rows + names.size() * (size_t)W : f.rows[r].data());
+            names.push_back(&f.names[r]);
         }
-    if (!out) { fprintf(stderr, "ERROR: Failed to write file: %s\n", outFile.c_str()); exit(1); }
+    io::writeRecords(outFile, names, rowAt, W);
 }
 
 }  // namespace
@@ -89,15 +87,8 @@ int runMerge(Option &option)
         MsaFile &f = files[k];
         f.path = paths[k];
         f.firstId = nRows;
-        io::readRecords(f.path, [&](std::string &name, std::string &seq) { f.names.push_back(name); f.rows.push_back(std::move(seq)); });
-        if (f.rows.empty()) { std::cerr << "ERROR: no rows were read from " << f.path << ".\n"; exit(1); }
-        f.L = (int32_t)f.rows[0].size();
-        for (size_t r = 1; r < f.rows.size(); ++r)
-            if ((int32_t)f.rows[r].size() != f.L) {
-                std::cerr << "ERROR: length of \"" << f.names[r] << "\" (" << f.rows[r].size() << ") does not match in " << f.path << " (" << f.L
-                          << "): the rows of an alignment must all have one length.\n";
-                exit(1);
-            }
+        f.L = io::readAlignedRows(f.path, "an alignment", f.names, f.rows);
+        if (f.L < 0) { std::cerr << "ERROR: no rows were read from " << f.path << ".\n"; exit(1); }
         if (f.L == 0) { std::cerr << "ERROR: the rows of " << f.path << " have no columns.\n"; exit(1); }
         nRows += (int32_t)f.rows.size();
         std::cerr << '[' << k + 1 << '/' << paths.size() << "] " << fs::path(f.path).filename().string() << " (Count: " << f.rows.size() << ", Length: " << f.L << ")\n";
@@ -141,10 +132,6 @@ int runMerge(Option &option)
     const twl_params tp = baseParams(param);
     twl_params tz = tp;
     tz.gap_char = 0;                                       // alignment-cpu.cpp:88 (currentTask 2)
-    const bool removal = !(option.gappyVertical == 1.0f);
-    static const char bases[] = {'A', 'C', 'G', 'T', 'N'};
-    static const char acids[] = {'A', 'C', 'D', 'E', 'F', 'G', 'H', 'I', 'K', 'L', 'M', 'N', 'P', 'Q', 'R', 'S', 'T', 'V', 'W', 'Y', 'X'};
-    const char *letters = (option.type == 'n') ? bases : acids;
 
     // ---- one level per child, the last child first ----
     for (int32_t at = G - 1; at >= 1; --at) {
@@ -153,57 +140,24 @@ int runMerge(Option &option)
         const float qWeight = (float)qNum;
         const int32_t maxLen = std::max(rootLen, qLen);
         const twl_side sides[2] = {twl_side{0, 0, rootLen, rootNum, rootWeight, root, -1, 0}, twl_side{0, 0, qLen, qNum, qWeight, child, -1, 0}};
+        const int32_t sideLen[2] = {rootLen, qLen};
         int32_t lenOut[2] = {0, 0}, alnLen = 0;
         int16_t err = 0;
         double t0 = nowMs();
         if ((rc = twl_level_prepare(st, &tp, option.gappyVertical, 1, sides, nullptr, nullptr, maxLen, lenOut, nullptr)) != TWL_OK) die("twl_level_prepare", rc);
-        twl_stats ss{};
-        auto runOnce = [&](const twl_params &prm) {
-            if ((rc = twl_level_align(st, &prm, nullptr, nullptr, &alnLen, &err)) != TWL_OK) die("twl_level_align", rc);
-            if (twl_get_stats(device, &ss) == TWL_OK) { tot.cells += ss.band_cells; tot.kernel += ss.kernel_ms; }
-            return err;
-        };
-        runOnce(tz);
-        {   // alignment-cpu.cpp:95-128 with currentTask 2: retried until errorType 0
-            twl_params tr = tz;
-            progressive::retryUntilPassed(tr, err, std::min(lenOut[0], lenOut[1]), [&](const twl_params &grown) {
-                ++tot.retries;
-                if (option.printDetail) std::cout << "Retry alignment " << fs::path(files[child].path).filename().string() << "\txdrop " << grown.xdrop << " flen " << grown.flen << '\n';
-                return runOnce(grown);
-            });
-        }
+        // alignment-cpu.cpp:95-128 with currentTask 2: retried until errorType 0
+        const std::string what = "alignment " + fs::path(files[child].path).filename().string();
+        alignWithRetry(st, device, tz, option, &what, nullptr, std::min(lenOut[0], lenOut[1]), &alnLen, &err, tot.run);
         tot.dp += nowMs() - t0;
 
         // gappy columns back (alignment-helper.cpp:324-375) when a side lost a column; otherwise the path is final as the DP left it
         t0 = nowMs();
         const int32_t stride = rootLen + qLen;
-        uint8_t fromDp = 1;
-        int32_t pathLen = alnLen;
-        if (lenOut[0] < rootLen || lenOut[1] < qLen) {
-            const int32_t sel = 0;
-            int32_t fin = -1;
-            if ((rc = twl_level_restore(st, &tp, 1, &sel, stride, &fin)) != TWL_OK) die("twl_level_restore", rc);
-            if (fin > 0) pathLen = fin;
-            else {      // a two-sided run too large for the device: restored on the host, into the level's path buffer
-                const size_t sl = (size_t)maxLen;
-                std::vector<uint8_t> info(2 * sl);
-                std::vector<int8_t> raw(2 * sl);
-                if ((rc = twl_level_read_colinfo_many(st, 1, &sel, info.data())) != TWL_OK) die("twl_level_read_colinfo_many", rc);
-                if ((rc = twl_level_read_paths(st, 1, &sel, &alnLen, raw.data(), (int32_t)(2 * sl))) != TWL_OK) die("twl_level_read_paths", rc);
-                std::pair<IntPairVec, IntPairVec> gappy;
-                stringPair cons;
-                runsAndConsensus(&info[0], rootLen, removal, letters, gappy.first, cons.first);
-                runsAndConsensus(&info[sl], qLen, removal, letters, gappy.second, cons.second);
-                alnPath path(raw.data(), raw.data() + alnLen), full;
-                int alnRef = 0, alnQry = 0;
-                for (auto a : path) { if (a != 1) ++alnRef; if (a != 2) ++alnQry; }
-                alignment_helper::addGappyColumnsBack(path, full, gappy, param, {alnRef, alnQry}, cons);
-                if ((int32_t)full.size() > stride) { std::cerr << "ERROR: path longer than both sides together.\n"; exit(1); }
-                if ((rc = twl_level_write_final(st, 0, full.data(), (int32_t)full.size())) != TWL_OK) die("twl_level_write_final", rc);
-                pathLen = (int32_t)full.size();
-            }
-            fromDp = 2;
-        }
+        const progressive::gpu::AlignedLevel al{1, sideLen, lenOut, &alnLen, &err, maxLen, stride};
+        const progressive::gpu::FinalPaths fin = finalPathsOfLevel(st, tp, param, option, al);
+        const uint8_t fromDp = fin.fromDp[0];
+        const int32_t pathLen = fin.pathLen[0];
+        tot.restoredOnHost += fin.restoredOnHost;
         tot.restore += nowMs() - t0;
 
         // the maps of the files under both sides, then the two profiles (updateAlignment / updateFrequency, alignment-cpu.cpp:169-170)
@@ -238,11 +192,11 @@ int runMerge(Option &option)
     t = nowMs();
     writeRecords(option.outFile, files, rows.data(), W);
     tot.write = nowMs() - t;
-    std::cerr << "Merged " << G << " alignments (" << nRows << " rows): final alignment length " << W << ", " << tot.retries << " retried DP run(s)\n";
+    std::cerr << "Merged " << G << " alignments (" << nRows << " rows): final alignment length " << W << ", " << tot.run.retries << " retried DP run(s)\n";
     if (option.printDetail)
         fprintf(stderr, "Merge phases (ms): count %.3f, prepare+DP %.3f, restore %.3f, apply %.3f, commit %.3f, finish %.3f, read-back %.3f, write %.3f; "
-                        "DP kernel %.3f ms, %llu band cells\n", tot.count, tot.dp, tot.restore, tot.apply, tot.commit, tot.finish, tot.read, tot.write, tot.kernel,
-                (unsigned long long)tot.cells);
+                        "DP kernel %.3f ms, %llu band cells; restored on the host %d\n", tot.count, tot.dp, tot.restore, tot.apply, tot.commit, tot.finish, tot.read, tot.write,
+                tot.run.kernel, (unsigned long long)tot.run.cells, tot.restoredOnHost);
     return W;
 }
 

@@ -16,7 +16,6 @@
 
 #include <algorithm>
 #include <cstdio>
-#include <fstream>
 #include <iostream>
 #include <numeric>
 #include <string>
@@ -27,7 +26,8 @@ namespace msa {
 using progressive::gpu::baseParams;
 using progressive::gpu::die;
 using progressive::gpu::nowMs;
-using progressive::gpu::runsAndConsensus;
+using progressive::gpu::alignWithRetry;
+using progressive::gpu::finalPathsOfLevel;
 
 namespace {
 
@@ -36,7 +36,7 @@ namespace {
 constexpr double kChunkBudget = 16.0 * (1 << 30);
 constexpr int kMaxChunk = 4096;
 
-struct Totals { double count = 0, dp = 0, restore = 0, collect = 0, finish = 0, read = 0, write = 0, kernel = 0; uint64_t cells = 0; int retries = 0; };
+struct Totals { double count = 0, dp = 0, restore = 0, collect = 0, finish = 0, read = 0, write = 0; progressive::gpu::DpTotals run; int restoredOnHost = 0; };
 
 }  // namespace
 
@@ -49,15 +49,8 @@ int runPlacement(Option &option)
 
     // ---- the backbone: every row must have the first row's length ----
     std::vector<std::string> bbNames, bbRows;
-    io::readRecords(option.backboneAlnFile, [&](std::string &name, std::string &seq) { bbNames.push_back(name); bbRows.push_back(std::move(seq)); });
-    if (bbRows.empty()) { std::cerr << "ERROR: no rows were read from the backbone alignment " << option.backboneAlnFile << ".\n"; exit(1); }
-    const int32_t L = (int32_t)bbRows[0].size();
-    for (size_t k = 1; k < bbRows.size(); ++k)
-        if ((int32_t)bbRows[k].size() != L) {
-            std::cerr << "ERROR: length of \"" << bbNames[k] << "\" (" << bbRows[k].size() << ") does not match in " << option.backboneAlnFile << " (" << L
-                      << "): the rows of a backbone alignment must all have one length.\n";
-            exit(1);
-        }
+    const int32_t L = io::readAlignedRows(option.backboneAlnFile, "a backbone alignment", bbNames, bbRows);
+    if (L < 0) { std::cerr << "ERROR: no rows were read from the backbone alignment " << option.backboneAlnFile << ".\n"; exit(1); }
     std::cerr << "==== Backbone Alignment ====\nNumber : " << bbRows.size() << "\nLength:  " << L << '\n';
 
     // ---- new sequences, read and flagged as readSequences does: the "tree" is the star of their names (twilight-main.cpp:214-217) ----
@@ -103,10 +96,6 @@ int runPlacement(Option &option)
     const twl_params tp = baseParams(param);
     twl_params tz = tp;
     tz.gap_char = 0;                                       // alignment-cpu.cpp:88 (currentTask 2)
-    const bool removal = !(option.gappyVertical == 1.0f);
-    static const char bases[] = {'A', 'C', 'G', 'T', 'N'};
-    static const char acids[] = {'A', 'C', 'D', 'E', 'F', 'G', 'H', 'I', 'K', 'L', 'M', 'N', 'P', 'Q', 'R', 'S', 'T', 'V', 'W', 'Y', 'X'};
-    const char *letters = (option.type == 'n') ? bases : acids;
     const int P = option.type == 'n' ? 6 : 22;
 
     // an empty sequence: L reference-only codes (alignment-cpu.cpp:90), straight from the host
@@ -134,76 +123,28 @@ int runPlacement(Option &option)
         for (int32_t id : ids) maxLen = std::max(maxLen, qlen(id));
         std::vector<twl_side> sides(2 * (size_t)n);
         std::vector<float> mw((size_t)n, 1.0f);           // seq.weight / groupWeight * num of a lone sequence
+        std::vector<int32_t> sideLen(2 * (size_t)n);
         for (int32_t i = 0; i < n; ++i) {
             sides[2 * i] = twl_side{0, 0, L, B, (float)B, kBackboneCache, -1, 0};
             sides[2 * i + 1] = twl_side{1, i, qlen(ids[i]), 1, 1.0f, -1, -1, 0};
+            sideLen[2 * i] = L; sideLen[2 * i + 1] = qlen(ids[i]);
         }
         std::vector<int32_t> lenOut(2 * (size_t)n), alnLen((size_t)n);
         std::vector<int16_t> err((size_t)n);
         double t0 = nowMs();
         if ((rc = twl_level_prepare(st, &tp, option.gappyVertical, n, sides.data(), ids.data(), mw.data(), maxLen, lenOut.data(), nullptr)) != TWL_OK) die("twl_level_prepare", rc);
-        twl_stats ss{};
-        if (!errIn) {
-            if ((rc = twl_level_align(st, &prm, nullptr, nullptr, alnLen.data(), err.data())) != TWL_OK) die("twl_level_align", rc);
-            if (twl_get_stats(device, &ss) == TWL_OK) { tot.cells += ss.band_cells; tot.kernel += ss.kernel_ms; }
-        } else {
-            // a pair that failed in its chunk (alignment-cpu.cpp:95-128 with currentTask != 0): alone, retried until errorType 0
-            twl_params tr = prm;
-            const int32_t minLen = std::min(lenOut[0], lenOut[1]);
-            progressive::retryUntilPassed(tr, (*errIn)[0], minLen, [&](const twl_params &grown) {
-                ++tot.retries;
-                if (option.printDetail) std::cout << "Retry sequence " << placed[ids[0] - B]->name << "\txdrop " << grown.xdrop << " flen " << grown.flen << '\n';
-                if ((rc = twl_level_align(st, &grown, nullptr, nullptr, alnLen.data(), err.data())) != TWL_OK) die("twl_level_align", rc);
-                if (twl_get_stats(device, &ss) == TWL_OK) { tot.cells += ss.band_cells; tot.kernel += ss.kernel_ms; }
-                return err[0];
-            });
-        }
+        // a pair that failed in its chunk (alignment-cpu.cpp:95-128 with currentTask != 0): alone, retried until errorType 0
+        const std::string what = errIn ? "sequence " + placed[ids[0] - B]->name : std::string();
+        alignWithRetry(st, device, prm, option, errIn ? &what : nullptr, errIn ? errIn->data() : nullptr, std::min(lenOut[0], lenOut[1]), alnLen.data(), err.data(), tot.run);
         tot.dp += nowMs() - t0;
         // gappy columns back (alignment-helper.cpp:324-375) for the pairs that lost a column; the others are final as the DP left them
         t0 = nowMs();
-        const int32_t stride = L + maxLen;
-        std::vector<uint8_t> fromDp((size_t)n, 0);
-        std::vector<int32_t> pathLen((size_t)n, 0), sel;
-        for (int32_t i = 0; i < n; ++i) {
-            if (err[i] != 0) continue;
-            pathLen[i] = alnLen[i];
-            fromDp[i] = 1;
-            if (lenOut[2 * i] < L || lenOut[2 * i + 1] < qlen(ids[i])) sel.push_back(i);
-        }
-        if (!sel.empty()) {
-            std::vector<int32_t> fin(sel.size(), -1);
-            if ((rc = twl_level_restore(st, &tp, (int32_t)sel.size(), sel.data(), stride, fin.data())) != TWL_OK) die("twl_level_restore", rc);
-            std::vector<int32_t> host, hostLen;
-            for (size_t k = 0; k < sel.size(); ++k) {
-                if (fin[k] > 0) { fromDp[sel[k]] = 2; pathLen[sel[k]] = fin[k]; }
-                else { host.push_back(sel[k]); hostLen.push_back(alnLen[sel[k]]); }
-            }
-            if (!host.empty()) {      // (rare: a two-sided run too large for the device) on the host, into the level's path buffer
-                const size_t sl = (size_t)maxLen;
-                std::vector<uint8_t> info(host.size() * 2 * sl);
-                std::vector<int8_t> raw(host.size() * 2 * sl);
-                if ((rc = twl_level_read_colinfo_many(st, (int32_t)host.size(), host.data(), info.data())) != TWL_OK) die("twl_level_read_colinfo_many", rc);
-                if ((rc = twl_level_read_paths(st, (int32_t)host.size(), host.data(), hostLen.data(), raw.data(), (int32_t)(2 * sl))) != TWL_OK) die("twl_level_read_paths", rc);
-                for (size_t k = 0; k < host.size(); ++k) {
-                    const int32_t i = host[k];
-                    std::pair<IntPairVec, IntPairVec> gappy;
-                    stringPair cons;
-                    runsAndConsensus(&info[2 * k * sl], L, removal, letters, gappy.first, cons.first);
-                    runsAndConsensus(&info[(2 * k + 1) * sl], qlen(ids[i]), removal, letters, gappy.second, cons.second);
-                    alnPath path(&raw[2 * k * sl], &raw[2 * k * sl] + hostLen[k]), full;
-                    int alnRef = 0, alnQry = 0;
-                    for (auto a : path) { if (a != 1) ++alnRef; if (a != 2) ++alnQry; }
-                    alignment_helper::addGappyColumnsBack(path, full, gappy, param, {alnRef, alnQry}, cons);
-                    if ((int32_t)full.size() > stride) { std::cerr << "ERROR: path longer than both sides together.\n"; exit(1); }
-                    if ((rc = twl_level_write_final(st, i, full.data(), (int32_t)full.size())) != TWL_OK) die("twl_level_write_final", rc);
-                    fromDp[i] = 2;
-                    pathLen[i] = (int32_t)full.size();
-                }
-            }
-        }
+        const progressive::gpu::AlignedLevel al{n, sideLen.data(), lenOut.data(), alnLen.data(), err.data(), maxLen, L + maxLen};
+        const progressive::gpu::FinalPaths fin = finalPathsOfLevel(st, tp, param, option, al);
+        tot.restoredOnHost += fin.restoredOnHost;
         tot.restore += nowMs() - t0;
         t0 = nowMs();
-        if ((rc = twl_place_collect(pl, st, n, ids.data(), nullptr, pathLen.data(), stride, fromDp.data())) != TWL_OK) die("twl_place_collect", rc);
+        if ((rc = twl_place_collect(pl, st, n, ids.data(), nullptr, fin.pathLen.data(), al.pathStride, fin.fromDp.data())) != TWL_OK) die("twl_place_collect", rc);
         tot.collect += nowMs() - t0;
         return err;
     };
@@ -241,22 +182,18 @@ int runPlacement(Option &option)
     twl_store_destroy(st);
     t = nowMs();
     {
-        std::ofstream out(option.outFile, std::ios::binary);
-        if (!out) { fprintf(stderr, "ERROR: Failed to open file: %s\n", option.outFile.c_str()); exit(1); }
-        for (size_t k = 0; k < outIds.size(); ++k) {
-            out << '>' << (k < (size_t)B ? bbNames[k] : placed[k - B]->name) << '\n';
-            out.write(&rows[k * (size_t)W], W);
-            out << '\n';
-        }
-        if (!out) { fprintf(stderr, "ERROR: Failed to write file: %s\n", option.outFile.c_str()); exit(1); }
+        std::vector<const std::string *> names;
+        std::vector<const char *> rowAt;
+        for (size_t k = 0; k < outIds.size(); ++k) { names.push_back(k < (size_t)B ? &bbNames[k] : &placed[k - B]->name); rowAt.push_back(&rows[k * (size_t)W]); }
+        io::writeRecords(option.outFile, names, rowAt, W);
     }
     tot.write = nowMs() - t;
     std::cerr << "Placed " << M << " sequences into " << B << " backbone rows: final alignment length " << W << " (backbone " << L << "), "
-              << nChunks << " chunk(s) of at most " << chunk << ", " << tot.retries << " retried DP run(s)\n";
+              << nChunks << " chunk(s) of at most " << chunk << ", " << tot.run.retries << " retried DP run(s)\n";
     if (option.printDetail)
         fprintf(stderr, "Placement phases (ms): count %.3f, prepare+DP %.3f, restore %.3f, collect %.3f, finish %.3f, read-back %.3f, write %.3f; "
-                        "DP kernel %.3f ms, %llu band cells\n", tot.count, tot.dp, tot.restore, tot.collect, tot.finish, tot.read, tot.write, tot.kernel,
-                (unsigned long long)tot.cells);
+                        "DP kernel %.3f ms, %llu band cells; restored on the host %d\n", tot.count, tot.dp, tot.restore, tot.collect, tot.finish, tot.read, tot.write,
+                tot.run.kernel, (unsigned long long)tot.run.cells, tot.restoredOnHost);
     return W;
 }
 

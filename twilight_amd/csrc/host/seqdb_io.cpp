@@ -350,6 +350,20 @@ void readRecords(const std::string &fileName, const std::function<void(std::stri
     gzclose(f);
 }
 
+int32_t readAlignedRows(const std::string &fileName, const char *kind, std::vector<std::string> &names, std::vector<std::string> &rows)
+{
+    readRecords(fileName, [&](std::string &name, std::string &seq) { names.push_back(name); rows.push_back(std::move(seq)); });
+    if (rows.empty()) return -1;
+    const int32_t L = (int32_t)rows[0].size();
+    for (size_t k = 1; k < rows.size(); ++k)
+        if ((int32_t)rows[k].size() != L) {
+            std::cerr << "ERROR: length of \"" << names[k] << "\" (" << rows[k].size() << ") does not match in " << fileName << " (" << L
+                      << "): the rows of " << kind << " must all have one length.\n";
+            exit(1);
+        }
+    return L;
+}
+
 char detectType(const std::string &seqFile)         // option.cpp:115-171: first decisive letter in the first 100 sequence lines
 {
     gzFile f = gzopen(seqFile.c_str(), "r");
@@ -440,16 +454,27 @@ void readSequences(const std::string &fileName, SequenceDB *database, Option *op
               << (option->noFilter ? "Deferred sequences: " : "Excluded sequences: ") << numLowQ << '\n';
 }
 
+static void writeRow(std::ostream &out, const std::string &name, const char *row, int len)
+{
+    out << '>' << name << '\n';
+    out.write(row, len);
+    out << '\n';
+}
+
 void writeAlignment(const std::string &fileName, SequenceDB *database, int alnLen)     // io.cpp:512-525 (plain FASTA, input order)
 {
     std::ofstream out(fileName, std::ios::binary);
     if (!out) { fprintf(stderr, "ERROR: Failed to open file: %s\n", fileName.c_str()); exit(1); }
-    for (auto *s : database->sequences) {
-        if (s->lowQuality) continue;
-        out << '>' << s->name << "\n";
-        out.write(&s->alnStorage[s->storage][0], alnLen);
-        out << '\n';
-    }
+    for (auto *s : database->sequences)
+        if (!s->lowQuality) writeRow(out, s->name, &s->alnStorage[s->storage][0], alnLen);
+}
+
+void writeRecords(const std::string &fileName, const std::vector<const std::string *> &names, const std::vector<const char *> &rows, int W)
+{
+    std::ofstream out(fileName, std::ios::binary);
+    if (!out) { fprintf(stderr, "ERROR: Failed to open file: %s\n", fileName.c_str()); exit(1); }
+    for (size_t k = 0; k < names.size(); ++k) writeRow(out, *names[k], rows[k], W);
+    if (!out) { fprintf(stderr, "ERROR: Failed to write file: %s\n", fileName.c_str()); exit(1); }
 }
 
 void writeFinalMSA(SequenceDB *database, Option *option, int alnLen)                  // io.cpp:465-488, DEFAULT_ALN branch

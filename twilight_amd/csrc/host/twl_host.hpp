@@ -197,6 +197,11 @@ void writeFinalMSA(SequenceDB *database, Option *option, int alnLen);
 char detectType(const std::string &seqFile);
 // every record of a FASTA(.gz) file, in file order, as readSequences sees them: each(name, sequence)
 void readRecords(const std::string &fileName, const std::function<void(std::string &, std::string &)> &each);
+// every record of an alignment file (`kind`: "a backbone alignment", "an alignment"); returns the one length of its rows, -1 for a file without
+// records; rows of two lengths end the run
+int32_t readAlignedRows(const std::string &fileName, const char *kind, std::vector<std::string> &names, std::vector<std::string> &rows);
+// plain FASTA of rows that all have W columns: record k is names[k] and the W bytes at rows[k]
+void writeRecords(const std::string &fileName, const std::vector<const std::string *> &names, const std::vector<const char *> &rows, int W);
 }  // namespace io
 
 using alnFunction = std::function<void(Tree *, NodePairVec &, SequenceDB *, Option *, Params &)>;

@@ -34,10 +34,7 @@ __global__ void __launch_bounds__(kPlThreads) merge_iota_kernel(const int64_t *p
 // the totals are carried over the rounds and tiles.  A rank at or beyond the side's width is counted but not stored: counts[t] = {codes
 // != 1, codes != 2, a code outside 0..2 seen}, which the host checks before anything is composed.
 struct RankArgs {
-    const int8_t *src[3];        // [0] host rows (uploaded), [1] DP output, [2] staged path buffer
-    const uint8_t *which;        // [n] index into src
-    const int64_t *src_off;      // [n]
-    const int32_t *plen;         // [n]
+    PathSrc from;                // [n] where every path lives (place_kernels.hip.h)
     const int32_t *wr, *wq;      // [n] width of the reference / query side
     const int64_t *r_off, *q_off;   // [n] where rpos / qpos start in ranks
     int32_t *ranks;
@@ -50,8 +47,8 @@ __global__ void __launch_bounds__(kPlThreads) merge_ranks_kernel(RankArgs a)
     __shared__ int s_wave[2][2][kPlThreads / 64];
     __shared__ int s_bad;
     const int t = blockIdx.x;
-    const int8_t *path = a.src[a.which[t]] + a.src_off[t];
-    const int32_t n = a.plen[t], wr = a.wr[t], wq = a.wq[t];
+    const int8_t *path = a.from.path(t);
+    const int32_t n = a.from.plen[t], wr = a.wr[t], wq = a.wq[t];
     int32_t *rpos = a.ranks + a.r_off[t], *qpos = a.ranks + a.q_off[t];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const unsigned long long below = (1ull << lane) - 1ull;

@@ -131,14 +131,20 @@ __device__ void scan_path(const int8_t *path, int32_t n, Stage stage, F f, int *
     *tot_q = Q;
 }
 
-// grid: n_pairs, 256 threads.  Pair t's final path (DP output, the staged path buffer or an uploaded host row: src_off[t] into src_base[t]'s
-// buffer) is copied to its sequence's slot of the placement's arena, and every insertion run folded into longest[c] (atomicMax at the run's
-// last code).  bad[t] = 1 when the path does not cover exactly L backbone columns and len[t] letters (nothing is folded then).
-struct CollectArgs {
+// Where the final paths of a call's taking pairs live (twl_place_collect, twl_merge_apply): pair t's path is plen[t] codes at src_off[t] of the
+// buffer which[t] names.
+struct PathSrc {
     const int8_t *src[3];        // [0] host rows (uploaded), [1] DP output, [2] staged path buffer
     const uint8_t *which;        // [n_pairs] index into src
     const int64_t *src_off;      // [n_pairs]
     const int32_t *plen;         // [n_pairs]
+    __device__ const int8_t *path(int t) const { return src[which[t]] + src_off[t]; }
+};
+
+// grid: n_pairs, 256 threads.  Pair t's final path (DP output, the staged path buffer or an uploaded host row: PathSrc) is copied
+// to its sequence's slot of the placement's arena, and every insertion run folded into longest[c] (atomicMax at the run's last code).  bad[t] = 1 when the path does not cover exactly L backbone columns and len[t] letters (nothing is folded then).
+struct CollectArgs {
+    PathSrc from;
     const int32_t *qlen;         // [n_pairs] letters of the sequence
     const int64_t *dst_off;      // [n_pairs] offset of the sequence's slot in the arena
     int8_t *arena;
@@ -151,8 +157,8 @@ __global__ void __launch_bounds__(kPlThreads) place_collect_kernel(CollectArgs a
 {
     __shared__ int s_ok;
     const int t = blockIdx.x;
-    const int8_t *path = a.src[a.which[t]] + a.src_off[t];
-    const int32_t n = a.plen[t];
+    const int8_t *path = a.from.path(t);
+    const int32_t n = a.from.plen[t];
     int8_t *dst = a.arena + a.dst_off[t];
     int tc, tq;
     // first pass: copy + totals (the folding must not see a path of another shape)

@@ -76,14 +76,8 @@ int twl_merge_apply(twl_merge *mg, twl_store *s, int32_t n_pairs, const int32_t 
                     const int32_t *qry_groups, const int8_t *paths, const int32_t *path_len, int32_t path_stride, const uint8_t *from_dp)
 {
     if (!mg || !s || mg->s != s) { g_err = "bad argument"; return TWL_ERR_BAD_ARGUMENT; }
-    MergeLevelView lv;
-    lv.prepared = s->prepared && s->lv;
-    lv.n_pairs = s->n_pairs;
-    lv.dp_stride = 2 * (int64_t)s->seq_len;
-    lv.has_dp = lv.prepared && s->lv->d_aln.p;
-    lv.staged_stride = s->staged_stride;
     MergeApplyPlan p;
-    if (const char *why = check_merge_apply(mg->g, mg->finished, n_pairs, ref_off, ref_groups, qry_off, qry_groups, paths != nullptr, path_len, path_stride, from_dp, lv, p)) {
+    if (const char *why = check_merge_apply(mg->g, mg->finished, n_pairs, ref_off, ref_groups, qry_off, qry_groups, paths != nullptr, path_len, path_stride, from_dp, path_level_view(s), p)) {
         g_err = why;
         return TWL_ERR_BAD_ARGUMENT;
     }
@@ -92,27 +86,17 @@ int twl_merge_apply(twl_merge *mg, twl_store *s, int32_t n_pairs, const int32_t 
     DEVICE_CALL(call, s->d);
     hipStream_t st = call.st;
     int rc;
-    if (!p.hostRows.empty()) {
-        if ((rc = mg->hostRows.ensure(p.hostRows.size() * (size_t)path_stride))) return rc;
-        for (size_t k = 0; k < p.hostRows.size(); ++k)
-            HIP_TRY(hipMemcpyAsync((int8_t *)mg->hostRows.p + k * (size_t)path_stride, paths + (size_t)p.hostRows[k] * (size_t)path_stride,
-                                   (size_t)path_len[p.hostRows[k]], hipMemcpyHostToDevice, st));
-    }
+    if ((rc = upload_host_paths(mg->hostRows, paths, path_len, path_stride, p.src.hostRows, st))) return rc;
     Ref rWhich, rSrc, rPlen, rWr, rWq, rROff, rQOff, rJobs;
     Arena &A = mg->up;
     if ((rc = A.begin((size_t)m * (1 + 3 * sizeof(int64_t) + 3 * sizeof(int32_t)) + p.jobs.size() * sizeof(ComposeRow), 8))) return rc;
-    A.put(rWhich, p.which); A.put(rSrc, p.srcOff); A.put(rPlen, p.plen); A.put(rWr, p.wr); A.put(rWq, p.wq); A.put(rROff, p.rOff); A.put(rQOff, p.qOff);
+    A.put(rWhich, p.src.which); A.put(rSrc, p.src.srcOff); A.put(rPlen, p.plen); A.put(rWr, p.wr); A.put(rWq, p.wq); A.put(rROff, p.rOff); A.put(rQOff, p.qOff);
     A.put(rJobs, p.jobs);
     if ((rc = A.flush(st))) return rc;
     if ((rc = mg->ranks.ensure((size_t)std::max<int64_t>(p.rankInts, 4) * sizeof(int32_t)))) return rc;
     if ((rc = mg->counts.ensure((size_t)m * 3 * sizeof(int32_t)))) return rc;
     twl::RankArgs a{};
-    a.src[0] = (const int8_t *)mg->hostRows.p;
-    a.src[1] = from_dp ? (const int8_t *)s->lv->d_aln.p : nullptr;
-    a.src[2] = from_dp ? (const int8_t *)s->lv->d_paths.p : nullptr;
-    a.which = rWhich.as<const uint8_t>();
-    a.src_off = rSrc.as<const int64_t>();
-    a.plen = rPlen.as<const int32_t>();
+    a.from = path_src(s, from_dp, mg->hostRows, rWhich, rSrc, rPlen);
     a.wr = rWr.as<const int32_t>(); a.wq = rWq.as<const int32_t>();
     a.r_off = rROff.as<const int64_t>(); a.q_off = rQOff.as<const int64_t>();
     a.ranks = (int32_t *)mg->ranks.p;
@@ -170,9 +154,7 @@ int twl_merge_finish(twl_merge *mg, int32_t *W_out)
         A.put(rIds, g.rows); A.put(rPlane, plane); A.put(rSG, sGroup); A.put(rSF, sFirst); A.put(rSN, sN);
         if ((rc = A.flush(st))) return rc;
         twl::RewriteArgs a{};
-        a.rows0 = (const char *)s->rows[0].p; a.rows1 = (const char *)s->rows[1].p;
-        a.out0 = (char *)s->rows[0].p; a.out1 = (char *)s->rows[1].p;
-        a.cap = s->cap;
+        fill_row_planes(s, a);
         a.ids = rIds.as<const int32_t>(); a.plane = rPlane.as<const uint8_t>();
         a.slice_group = rSG.as<const int32_t>(); a.slice_first = rSF.as<const int32_t>(); a.slice_n = rSN.as<const int32_t>();
         a.L = mg->rL.as<const int32_t>();
@@ -187,7 +169,7 @@ int twl_merge_finish(twl_merge *mg, int32_t *W_out)
         float ms = 0;
         if (hipEventElapsedTime(&ms, mg->ev[2], mg->ev[4]) == hipSuccess) mg->finish_ms = ms;
         if (hipEventElapsedTime(&ms, mg->ev[3], mg->ev[4]) == hipSuccess) mg->rewrite_ms = ms;
-        for (int32_t q : g.rows) { s->plane[q] ^= 1; s->len[q] = W; }
+        rows_rewritten(s, g.rows, W);
     }
     mg->finished = true;
     *W_out = W;

@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <vector>
 #include "../../include/twl_merge.h"
+#include "twl_path_source.inc.hip"
 
 // The groups of a merge as the host knows them.
 struct MergeGroups {
@@ -50,24 +51,13 @@ inline const char *check_merge_create(int32_t n_groups, const int32_t *group_off
     return nullptr;
 }
 
-// What an apply needs to know of the store's level (from_dp != NULL reads its buffers).
-struct MergeLevelView {
-    bool prepared = false;       // a level is prepared and holds its buffers
-    int32_t n_pairs = 0;
-    int64_t dp_stride = 0;       // row pitch of the DP output (2 * seq_len)
-    bool has_dp = false;         // the DP output exists
-    int32_t staged_stride = 0;   // > 0: twl_level_restore staged the paths at this pitch
-};
-
 // One map to compose: pos[pos_off + c] = ranks[tab_off + pos[pos_off + c]] for c < L.  Field for field twl::ComposeJob (merge_kernels.hip.h).
 struct ComposeRow { int64_t pos_off, tab_off; int32_t L, tab_len; };
 
 struct MergeApplyPlan {
     std::vector<int32_t> pair;           // the pairs that take part (path_len != 0), in order
     std::vector<int32_t> plen, wr, wq;   // per taking pair: path length, current width of its reference / query side
-    std::vector<uint8_t> which;          // per taking pair: 0 host row, 1 DP output, 2 path buffer
-    std::vector<int64_t> srcOff;         // per taking pair: offset of its path in that source
-    std::vector<int32_t> hostRows;       // pairs whose path comes from the host, in upload order
+    PathSources src;                     // per taking pair: where its path lives (twl_path_source.inc.hip)
     std::vector<int64_t> rOff, qOff;     // per taking pair: where rpos / qpos start in the rank arena, in ints
     int64_t rankInts = 0;
     std::vector<ComposeRow> jobs;        // one per group under a side of a taking pair
@@ -78,12 +68,12 @@ struct MergeApplyPlan {
 // Everything twl_merge_apply rejects before a path is looked at: the message, or nullptr with `p` filled in.
 inline const char *check_merge_apply(const MergeGroups &g, bool finished, int32_t n_pairs, const int32_t *ref_off, const int32_t *ref_groups, const int32_t *qry_off,
                                      const int32_t *qry_groups, bool havePaths, const int32_t *path_len, int32_t path_stride, const uint8_t *from_dp,
-                                     const MergeLevelView &lv, MergeApplyPlan &p)
+                                     const PathLevelView &lv, MergeApplyPlan &p)
 {
     p = MergeApplyPlan{};
     if (n_pairs < 0 || (n_pairs > 0 && (!ref_off || !qry_off || !ref_groups || !qry_groups || !path_len || path_stride < 1))) return "bad argument";
     if (finished) return "twl_merge_apply after twl_merge_finish";
-    if (from_dp && (!lv.prepared || lv.n_pairs != n_pairs)) return "from_dp needs the prepared and aligned level of these pairs";
+    if (const char *why = check_path_level(from_dp, n_pairs, lv)) return why;
     if (n_pairs > 0 && (ref_off[0] < 0 || qry_off[0] < 0)) return "bad group table";
     for (int32_t i = 0; i < n_pairs; ++i)
         if (ref_off[i + 1] < ref_off[i] || qry_off[i + 1] < qry_off[i]) return "bad group table";
@@ -105,15 +95,9 @@ inline const char *check_merge_apply(const MergeGroups &g, bool finished, int32_
             }
         }
         if (n < 0 || n > path_stride || (int64_t)n > (int64_t)w[0] + w[1]) return "path_len outside [0, min(path_stride, ref width + qry width)]";
-        const int src = from_dp ? from_dp[i] : 0;
-        if (src > 2) return "from_dp must be 0, 1 or 2";
-        if (src == 1 && ((int64_t)n > lv.dp_stride || !lv.has_dp)) return "from_dp 1 without a DP output of that length";
-        if (src == 2 && (!lv.staged_stride || lv.staged_stride != path_stride)) return "from_dp 2: twl_level_restore first, with this row pitch";
-        if (src == 0 && !havePaths) return "host rows missing";
+        if (const char *why = add_path_source(p.src, i, n, from_dp, havePaths, path_stride, lv)) return why;
         const int32_t at = (int32_t)p.pair.size();
-        p.pair.push_back(i); p.plen.push_back(n); p.wr.push_back(w[0]); p.wq.push_back(w[1]); p.which.push_back((uint8_t)src);
-        if (src == 0) { p.srcOff.push_back((int64_t)p.hostRows.size() * path_stride); p.hostRows.push_back(i); }
-        else p.srcOff.push_back((int64_t)i * (src == 1 ? lv.dp_stride : (int64_t)path_stride));
+        p.pair.push_back(i); p.plen.push_back(n); p.wr.push_back(w[0]); p.wq.push_back(w[1]);
         p.rOff.push_back(p.rankInts); p.rankInts += w[0];
         p.qOff.push_back(p.rankInts); p.rankInts += w[1];
         for (int side = 0; side < 2; ++side) {

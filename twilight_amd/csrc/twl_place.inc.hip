@@ -4,32 +4,31 @@
 // HBM of a placement: one arena of final paths (a slot of L + len bytes per sequence of the store), longest[L + 1], and at the finish
 // ins[L + 1] and colsrc[W] (kernels: place_kernels.hip.h).
 
-#include <unordered_set>
+// What a call rejects, and the placement's bookkeeping, are decided in twl_place_plan.inc.hip (pure); this file allocates, uploads, launches
+// and reads back.
+
+#include "twl_place_plan.inc.hip"
 
 struct twl_place {
     twl_store *s = nullptr;
-    int32_t L = 0;
-    bool finished = false;
-    std::vector<int32_t> qlen;       // length of every store sequence when the placement began (its path covers that many letters)
-    std::vector<int64_t> slot;       // its slot in the arena
-    std::vector<int32_t> plen;       // collected path length, -1: not collected
-    std::vector<int32_t> placed;     // collected ids, in order
+    PlaceBook b;
     Buf arena, longest, ins, colsrc, w, bad, hostRows;
     Arena up;                        // the small per-call tables of collect / finish: both synchronise the stream before they return
     PinBuf back;
+    void release()
+    {
+        for (Buf *buf : {&arena, &longest, &ins, &colsrc, &w, &bad, &hostRows}) buf->release();
+        up.release(); back.release();
+    }
 };
 
 extern "C" {
 
 int twl_store_count_columns(twl_store *s, int32_t n_ids, const int32_t *ids, int32_t cache_id)
 {
-    if (!s || n_ids < 1 || !ids || cache_id < 0) { g_err = "bad argument"; return TWL_ERR_BAD_ARGUMENT; }
-    if (s->cache.count(cache_id)) { g_err = "cache id in use"; return TWL_ERR_BAD_ARGUMENT; }
-    const int32_t L = (ids[0] >= 0 && ids[0] < s->n_seqs) ? s->len[ids[0]] : -1;
-    for (int32_t t = 0; t < n_ids; ++t) {
-        if (ids[t] < 0 || ids[t] >= s->n_seqs) { g_err = "sequence id out of range"; return TWL_ERR_BAD_ARGUMENT; }
-        if (s->len[ids[t]] != L) { g_err = "the rows to count differ in length"; return TWL_ERR_BAD_ARGUMENT; }
-    }
+    if (!s) { g_err = "bad argument"; return TWL_ERR_BAD_ARGUMENT; }
+    int32_t L = -1;
+    if (const char *why = check_count_columns(n_ids, ids, cache_id, cache_id >= 0 && s->cache.count(cache_id), s->n_seqs, s->len.data(), &L)) { g_err = why; return TWL_ERR_BAD_ARGUMENT; }
     DEVICE_CALL(call, s->d);
     hipStream_t st = call.st;
     const size_t P = (size_t)s->P, cells = (size_t)L * P;
@@ -62,22 +61,21 @@ int twl_store_count_columns(twl_store *s, int32_t n_ids, const int32_t *ids, int
 
 int twl_place_create(twl_store *s, int32_t L, twl_place **out)
 {
-    if (!s || L < 0 || !out) { g_err = "bad argument"; return TWL_ERR_BAD_ARGUMENT; }
-    DEVICE_CALL(call, s->d);
-    Device *d = call.d;
+    if (!s || !out) { g_err = "bad argument"; return TWL_ERR_BAD_ARGUMENT; }
     auto pl = std::make_unique<twl_place>();
-    pl->s = s;
-    pl->L = L;
-    pl->qlen = s->len;
-    pl->slot.resize((size_t)s->n_seqs);
-    pl->plen.assign((size_t)s->n_seqs, -1);
     int64_t total = 0;
-    for (int32_t i = 0; i < s->n_seqs; ++i) { pl->slot[i] = total; total += (int64_t)L + s->len[i]; }
+    if (const char *why = check_place_create(L, s->n_seqs, s->len.data(), pl->b, &total)) { g_err = why; return TWL_ERR_BAD_ARGUMENT; }
+    pl->s = s;
+    struct Undo { twl_place *p; ~Undo() { if (p) p->release(); } };      // (a create that fails gives back what it took)
+    DEVICE_CALL(call, s->d);
+    Undo undo{pl.get()};
+    hipStream_t st = call.st;
     int rc;
     if ((rc = pl->arena.ensure((size_t)std::max<int64_t>(total, 16)))) return rc;
     if ((rc = pl->longest.ensure(((size_t)L + 1) * sizeof(int32_t)))) return rc;
-    HIP_TRY(hipMemsetAsync(pl->longest.p, 0, ((size_t)L + 1) * sizeof(int32_t), d->stream));
-    HIP_TRY(hipStreamSynchronize(d->stream));
+    HIP_TRY(hipMemsetAsync(pl->longest.p, 0, ((size_t)L + 1) * sizeof(int32_t), st));
+    HIP_TRY(hipStreamSynchronize(st));
+    undo.p = nullptr;
     *out = pl.release();
     return TWL_OK;
 }
@@ -90,70 +88,39 @@ void twl_place_destroy(twl_place *pl)
         std::lock_guard<std::mutex> lk(pl->s->d->mu);
         (void)hipSetDevice(pl->s->d->id);
         (void)hipStreamSynchronize(pl->s->d->stream);
-        for (Buf *b : {&pl->arena, &pl->longest, &pl->ins, &pl->colsrc, &pl->w, &pl->bad, &pl->hostRows}) b->release();
-        pl->up.release();
-        pl->back.release();
+        pl->release();
     }
 }
 
 int twl_place_collect(twl_place *pl, twl_store *s, int32_t n_pairs, const int32_t *seq_ids, const int8_t *paths, const int32_t *path_len,
                       int32_t path_stride, const uint8_t *from_dp)
 {
-    if (!pl || !s || pl->s != s || n_pairs < 0 || (n_pairs > 0 && (!seq_ids || !path_len || path_stride < 1))) { g_err = "bad argument"; return TWL_ERR_BAD_ARGUMENT; }
-    if (pl->finished) { g_err = "twl_place_collect after twl_place_finish"; return TWL_ERR_BAD_ARGUMENT; }
-    if (from_dp && (!s->prepared || !s->lv || s->n_pairs != n_pairs)) { g_err = "from_dp needs the prepared and aligned level of these pairs"; return TWL_ERR_BAD_ARGUMENT; }
-    const int64_t dpStride = 2 * (int64_t)s->seq_len;
-    std::vector<int32_t> ids, plen, qlen;
-    std::vector<uint8_t> which;
-    std::vector<int64_t> srcOff, dstOff;
-    std::vector<int32_t> hostRows;                 // pairs whose row comes from `paths`
-    std::unordered_set<int32_t> seen;
-    for (int32_t i = 0; i < n_pairs; ++i) {
-        const int32_t id = seq_ids[i], n = path_len[i];
-        if (n == 0) continue;
-        if (id < 0 || id >= s->n_seqs) { g_err = "sequence id out of range"; return TWL_ERR_BAD_ARGUMENT; }
-        if (pl->plen[id] >= 0 || !seen.insert(id).second) { g_err = "sequence collected twice"; return TWL_ERR_BAD_ARGUMENT; }
-        if (s->len[id] != pl->qlen[id]) { g_err = "the sequence's row has been rewritten since the placement began"; return TWL_ERR_BAD_ARGUMENT; }
-        if (n < 0 || n > path_stride || (int64_t)n > (int64_t)pl->L + pl->qlen[id]) { g_err = "path_len outside [0, min(path_stride, L + len)]"; return TWL_ERR_BAD_ARGUMENT; }
-        const int w = from_dp ? from_dp[i] : 0;
-        if (w == 1 && ((int64_t)n > dpStride || !s->lv->d_aln.p)) { g_err = "from_dp 1 without a DP output of that length"; return TWL_ERR_BAD_ARGUMENT; }
-        if (w == 2 && (!s->staged_stride || s->staged_stride != path_stride)) { g_err = "from_dp 2: twl_level_restore first, with this row pitch"; return TWL_ERR_BAD_ARGUMENT; }
-        if (w == 0 && !paths) { g_err = "host rows missing"; return TWL_ERR_BAD_ARGUMENT; }
-        if (w > 2) { g_err = "from_dp must be 0, 1 or 2"; return TWL_ERR_BAD_ARGUMENT; }
-        ids.push_back(id); plen.push_back(n); qlen.push_back(pl->qlen[id]); which.push_back((uint8_t)w); dstOff.push_back(pl->slot[id]);
-        if (w == 0) { srcOff.push_back((int64_t)hostRows.size() * path_stride); hostRows.push_back(i); }
-        else srcOff.push_back((int64_t)i * (w == 1 ? dpStride : (int64_t)path_stride));
+    if (!pl || !s || pl->s != s) { g_err = "bad argument"; return TWL_ERR_BAD_ARGUMENT; }
+    PlaceCollectPlan p;
+    if (const char *why = check_place_collect(pl->b, n_pairs, seq_ids, paths != nullptr, path_len, path_stride, from_dp, s->n_seqs, s->len.data(), path_level_view(s), p)) {
+        g_err = why;
+        return TWL_ERR_BAD_ARGUMENT;
     }
     DEVICE_CALL(call, s->d);
     hipStream_t st = call.st;
     int rc;
-    const int32_t m = (int32_t)ids.size();
+    const int32_t m = (int32_t)p.ids.size();
     if (m > 0) {
-        if (!hostRows.empty()) {
-            if ((rc = pl->hostRows.ensure(hostRows.size() * (size_t)path_stride))) return rc;
-            for (size_t k = 0; k < hostRows.size(); ++k)
-                HIP_TRY(hipMemcpyAsync((int8_t *)pl->hostRows.p + k * (size_t)path_stride, paths + (size_t)hostRows[k] * (size_t)path_stride,
-                                       (size_t)path_len[hostRows[k]], hipMemcpyHostToDevice, st));
-        }
+        if ((rc = upload_host_paths(pl->hostRows, paths, path_len, path_stride, p.src.hostRows, st))) return rc;
         Ref rWhich, rSrc, rPlen, rQlen, rDst;
         Arena &A = pl->up;
         if ((rc = A.begin((size_t)m * (1 + 2 * sizeof(int64_t) + 2 * sizeof(int32_t)), 5))) return rc;
-        A.put(rWhich, which); A.put(rSrc, srcOff); A.put(rPlen, plen); A.put(rQlen, qlen); A.put(rDst, dstOff);
+        A.put(rWhich, p.src.which); A.put(rSrc, p.src.srcOff); A.put(rPlen, p.plen); A.put(rQlen, p.qlen); A.put(rDst, p.dstOff);
         if ((rc = A.flush(st))) return rc;
         if ((rc = pl->bad.ensure((size_t)m * sizeof(int32_t)))) return rc;
         twl::CollectArgs a{};
-        a.src[0] = (const int8_t *)pl->hostRows.p;
-        a.src[1] = from_dp ? (const int8_t *)s->lv->d_aln.p : nullptr;
-        a.src[2] = from_dp ? (const int8_t *)s->lv->d_paths.p : nullptr;
-        a.which = rWhich.as<const uint8_t>();
-        a.src_off = rSrc.as<const int64_t>();
-        a.plen = rPlen.as<const int32_t>();
+        a.from = path_src(s, from_dp, pl->hostRows, rWhich, rSrc, rPlen);
         a.qlen = rQlen.as<const int32_t>();
         a.dst_off = rDst.as<const int64_t>();
         a.arena = (int8_t *)pl->arena.p;
         a.longest = (int32_t *)pl->longest.p;
         a.bad = (int32_t *)pl->bad.p;
-        a.L = pl->L;
+        a.L = pl->b.L;
         hipLaunchKernelGGL(twl::place_collect_kernel, dim3((unsigned)m), dim3(twl::kPlThreads), 0, st, a);
         HIP_TRY(hipGetLastError());
         if ((rc = pl->back.ensure((size_t)m * sizeof(int32_t)))) return rc;
@@ -165,29 +132,20 @@ int twl_place_collect(twl_place *pl, twl_store *s, int32_t n_pairs, const int32_
         s->staged_stride = 0;
         release_level(s->lv);
     }
-    int32_t nBad = 0;
-    for (int32_t k = 0; k < m; ++k) {
-        if (((const int32_t *)pl->back.p)[k]) ++nBad;
-        else { pl->plen[ids[k]] = plen[k]; pl->placed.push_back(ids[k]); }
+    if (const int32_t nBad = place_collect_done(pl->b, p, (const int32_t *)pl->back.p)) {
+        g_err = std::string("a path does not cover the backbone's columns and its sequence's letters exactly (") + std::to_string(nBad) + " paths)";
+        return TWL_ERR_BAD_ARGUMENT;
     }
-    if (nBad) { g_err = "a path does not cover the backbone's columns and its sequence's letters exactly (" + std::to_string(nBad) + " paths)"; return TWL_ERR_BAD_ARGUMENT; }
     return TWL_OK;
 }
 
 int twl_place_finish(twl_place *pl, int32_t n_backbone, const int32_t *backbone_ids, int32_t *W_out)
 {
-    if (!pl || n_backbone < 0 || (n_backbone > 0 && !backbone_ids) || !W_out) { g_err = "bad argument"; return TWL_ERR_BAD_ARGUMENT; }
-    if (pl->finished) { g_err = "twl_place_finish called twice"; return TWL_ERR_BAD_ARGUMENT; }
+    if (!pl || !W_out) { g_err = "bad argument"; return TWL_ERR_BAD_ARGUMENT; }
     twl_store *s = pl->s;
-    const int32_t L = pl->L;
-    std::unordered_set<int32_t> seen(pl->placed.begin(), pl->placed.end());
-    for (int32_t t = 0; t < n_backbone; ++t) {
-        const int32_t id = backbone_ids[t];
-        if (id < 0 || id >= s->n_seqs || s->len[id] != L) { g_err = "backbone id out of range or not of length L"; return TWL_ERR_BAD_ARGUMENT; }
-        if (!seen.insert(id).second) { g_err = "a backbone id is listed twice or was collected"; return TWL_ERR_BAD_ARGUMENT; }
-    }
-    for (int32_t id : pl->placed)
-        if (s->len[id] != pl->qlen[id]) { g_err = "a placed sequence's row has been rewritten since it was collected"; return TWL_ERR_BAD_ARGUMENT; }
+    PlaceBook &b = pl->b;
+    if (const char *why = check_place_finish(b, n_backbone, backbone_ids, s->n_seqs, s->len.data())) { g_err = why; return TWL_ERR_BAD_ARGUMENT; }
+    const int32_t L = b.L;
     DEVICE_CALL(call, s->d);
     hipStream_t st = call.st;
     int rc;
@@ -199,7 +157,7 @@ int twl_place_finish(twl_place *pl, int32_t n_backbone, const int32_t *backbone_
     HIP_TRY(hipMemcpyAsync(pl->back.p, pl->w.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     const int32_t W = *(const int32_t *)pl->back.p;
-    if (W < L) { g_err = "final width below the backbone's"; return TWL_ERR_HIP; }
+    if (const char *why = check_place_width(b, W)) { g_err = why; return TWL_ERR_HIP; }
     if ((rc = wait_rows(s, st))) return rc;
     if ((rc = grow_rows(s, (int64_t)W + 1))) return rc;
     if ((rc = pl->colsrc.ensure((size_t)std::max(W, 1) * sizeof(int32_t)))) return rc;
@@ -207,11 +165,11 @@ int twl_place_finish(twl_place *pl, int32_t n_backbone, const int32_t *backbone_
     if (L > 0)
         hipLaunchKernelGGL(twl::place_colsrc_kernel, dim3((unsigned)((L + twl::kPlThreads - 1) / twl::kPlThreads)), dim3(twl::kPlThreads), 0, st,
                            (const int32_t *)pl->longest.p, (const int32_t *)pl->ins.p, L, (int32_t *)pl->colsrc.p);
-    const int32_t nP = (int32_t)pl->placed.size();
-    std::vector<int32_t> pIds(pl->placed), pQlen, pPlen, bIds(backbone_ids, backbone_ids + n_backbone);
+    const int32_t nP = (int32_t)b.placed.size();
+    std::vector<int32_t> pIds(b.placed), pQlen, pPlen, bIds(backbone_ids, backbone_ids + n_backbone);
     std::vector<uint8_t> pPlane, bPlane;
     std::vector<int64_t> pOff;
-    for (int32_t id : pIds) { pPlane.push_back(s->plane[id]); pQlen.push_back(pl->qlen[id]); pPlen.push_back(pl->plen[id]); pOff.push_back(pl->slot[id]); }
+    for (int32_t id : pIds) { pPlane.push_back(s->plane[id]); pQlen.push_back(b.qlen[id]); pPlen.push_back(b.plen[id]); pOff.push_back(b.slot[id]); }
     for (int32_t id : bIds) bPlane.push_back(s->plane[id]);
     Ref rPId, rPPl, rPQ, rPOff, rPLen, rBId, rBPl;
     Arena &A = pl->up;
@@ -219,9 +177,7 @@ int twl_place_finish(twl_place *pl, int32_t n_backbone, const int32_t *backbone_
     A.put(rPId, pIds); A.put(rPPl, pPlane); A.put(rPQ, pQlen); A.put(rPOff, pOff); A.put(rPLen, pPlen); A.put(rBId, bIds); A.put(rBPl, bPlane);
     if ((rc = A.flush(st))) return rc;
     twl::ExpandArgs a{};
-    a.rows0 = (const char *)s->rows[0].p; a.rows1 = (const char *)s->rows[1].p;
-    a.out0 = (char *)s->rows[0].p; a.out1 = (char *)s->rows[1].p;
-    a.cap = s->cap;
+    fill_row_planes(s, a);
     a.arena = (const int8_t *)pl->arena.p;
     a.longest = (const int32_t *)pl->longest.p; a.ins = (const int32_t *)pl->ins.p; a.colsrc = (const int32_t *)pl->colsrc.p;
     a.L = L; a.W = W;
@@ -238,9 +194,9 @@ int twl_place_finish(twl_place *pl, int32_t n_backbone, const int32_t *backbone_
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
-    for (int32_t id : pIds) { s->plane[id] ^= 1; s->len[id] = W; }
-    for (int32_t id : bIds) { s->plane[id] ^= 1; s->len[id] = W; }
-    pl->finished = true;
+    rows_rewritten(s, pIds, W);
+    rows_rewritten(s, bIds, W);
+    b.finished = true;
     *W_out = W;
     return TWL_OK;
 }
@@ -249,7 +205,7 @@ int twl_place_read_insertions(twl_place *pl, int32_t *out)
 {
     if (!pl || !out) { g_err = "bad argument"; return TWL_ERR_BAD_ARGUMENT; }
     DEVICE_CALL(call, pl->s->d);
-    HIP_TRY(hipMemcpyAsync(out, pl->longest.p, ((size_t)pl->L + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, call.st));
+    HIP_TRY(hipMemcpyAsync(out, pl->longest.p, ((size_t)pl->b.L + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, call.st));
     HIP_TRY(hipStreamSynchronize(call.st));
     return TWL_OK;
 }

@@ -8,6 +8,7 @@
 //   caches     one float[len][P] buffer per cached node profile (Node::msaFreq), addressed by the caller's ids.
 //   level      raw[2n][stride][P] -> cols[2n][stride][P+2] (what the DP kernel reads), colinfo[2n][stride], lens, paths.
 #include <cstdlib>
+#include "twl_path_source.inc.hip"
 
 namespace {
 
@@ -340,6 +341,39 @@ int wait_rows(twl_store *s, hipStream_t st)
 {
     if (s->rows_event) { HIP_TRY(hipStreamWaitEvent(st, s->rows_event, 0)); s->rows_event = nullptr; }
     return TWL_OK;
+}
+
+// The two ends of a kernel that rewrites whole rows into their other plane (the finish of a placement, of a merge): both planes as the
+// kernel's arguments name them, and behind the kernel the flag and the length of every rewritten row.
+template <class Args>
+void fill_row_planes(const twl_store *s, Args &a)
+{
+    a.rows0 = (const char *)s->rows[0].p; a.rows1 = (const char *)s->rows[1].p;
+    a.out0 = (char *)s->rows[0].p; a.out1 = (char *)s->rows[1].p;
+    a.cap = s->cap;
+}
+void rows_rewritten(twl_store *s, const std::vector<int32_t> &ids, int32_t W) { for (int32_t id : ids) { s->plane[id] ^= 1; s->len[id] = W; } }
+
+// ---- the store's level as the source of the final paths a call takes (twl_place_collect, twl_merge_apply; twl_path_source.inc.hip) ----
+PathLevelView path_level_view(const twl_store *s)
+{
+    const bool prepared = s->prepared && s->lv;
+    return PathLevelView{prepared, s->n_pairs, 2 * (int64_t)s->seq_len, prepared && s->lv->d_aln.p, s->staged_stride};
+}
+// the host rows of a call, packed at the call's pitch into `buf` in upload order
+int upload_host_paths(Buf &buf, const int8_t *paths, const int32_t *path_len, int32_t path_stride, const std::vector<int32_t> &hostRows, hipStream_t st)
+{
+    const size_t pitch = (size_t)path_stride;
+    if (!hostRows.empty()) { const int rc = buf.ensure(hostRows.size() * pitch); if (rc) return rc; }
+    for (size_t k = 0; k < hostRows.size(); ++k)
+        HIP_TRY(hipMemcpyAsync((int8_t *)buf.p + k * pitch, paths + (size_t)hostRows[k] * pitch, (size_t)path_len[hostRows[k]], hipMemcpyHostToDevice, st));
+    return TWL_OK;
+}
+// what the taking kernel reads: the three sources and the uploaded tables of the taking pairs
+twl::PathSrc path_src(const twl_store *s, const uint8_t *from_dp, const Buf &hostRows, const Ref &which, const Ref &srcOff, const Ref &plen)
+{
+    return twl::PathSrc{{(const int8_t *)hostRows.p, from_dp ? (const int8_t *)s->lv->d_aln.p : nullptr, from_dp ? (const int8_t *)s->lv->d_paths.p : nullptr},
+                        which.as<const uint8_t>(), srcOff.as<const int64_t>(), plen.as<const int32_t>()};
 }
 
 // ---- the one mover of rows: between the planes and a packed block of rows (row t at off[t]) on the host or on the device ----

@@ -173,7 +173,8 @@ int twl_comm_destroy(int device);
                              ones (up to 2 * CUs, one round of the throughput kernel) when they would fill that round badly
      TWL_KNOB_MT_MIN_MARKER  ... and only with marker >= this (default 512)
      TWL_KNOB_MT_LEAD        anti-diagonals a scout starts ahead of its tile boundary (default 320)
-     TWL_KNOB_MT_MARGIN      anti-diagonals a scout runs past its tile boundary (default 40)
+     TWL_KNOB_MT_MARGIN      anti-diagonals a scout runs past its tile boundary (default 40; 64 on levels of at most 2048 tile jobs).  A value >= 0 sets both kinds of
+                             level to it (at least 2); a negative value restores both defaults, 40 / 64
      TWL_KNOB_MT_ROUNDS      rounds of predict / run / verify before the remaining tiles are computed in line (default 2, at most 7)
      TWL_KNOB_MT_THR_JOBS    levels with more tiles than this run scouts and tiles on the throughput geometry (default 256 = the CUs)
      TWL_KNOB_FAIL_ROW_ALLOCS  the next n device allocations for the row planes of a store (include/twl_level.h) fail: tests of the
@@ -204,7 +205,8 @@ int twl_comm_destroy(int device);
      TWL_KNOB_MT_ANCHOR      1 (default): the scouts of the tile-parallel path (nucleotide and protein: the most frequent letter of a column) start from the cell on which the consensus letters of the two profiles agree
                              (one small kernel per level finds it for every tile boundary), TWL_KNOB_MT_LEAD2 (default 96) anti-diagonals ahead of the boundary, where
                              that cell is trusted; elsewhere, and with 0 everywhere, from the straight line between the corners TWL_KNOB_MT_LEAD ahead.  Predictions
-                             only: the results are the same either way (tests hold the two to each other)
+                             only: the results are the same either way (tests hold the two to each other).  TWL_KNOB_MT_LEAD2: 128 on levels of at most 2048 tile jobs;
+                             a value >= 0 sets both kinds of level to it (at least 16), a negative value restores both defaults, 96 / 128
      TWL_KNOB_PROT_CORRIDOR  rows (default 448): protein levels of few pairs precompute their column scores (matrix mode 4) only within this many rows of the straight line
                              between the corners of a pair's matrix; a pair whose band leaves that corridor is re-run by the kernel that scores in line.  0: the whole matrix */
 enum twl_knob { TWL_KNOB_MT_PERTURB = 1, TWL_KNOB_MT_MAX_PAIRS = 2, TWL_KNOB_MT_MIN_MARKER = 3, TWL_KNOB_MT_LEAD = 4, TWL_KNOB_MT_MARGIN = 5,

@@ -1,14 +1,17 @@
-// tests/policy_kats.cpp -- known answers of the re-run ladder (next_rung) and of the pass memory (PassMemory::update), which are pure functions in
-// twilight_amd/csrc/twl_policy.inc.hip (no HIP call: this program includes the file directly).  Every expected answer restates the dispatch of commit 4533235,
-// twilight_amd/csrc/twl_align.hip (run_device, lines 549-629), read as the specification; the line it restates is named.  Prints "OK <name>" / "FAIL <name>".
+// tests/policy_kats.cpp -- known answers of the re-run ladder (next_rung), of the pass memory (PassMemory::update) and of a tile-parallel level's plan (plan_tile_level),
+// which are pure functions in twilight_amd/csrc/twl_policy.inc.hip (no HIP call: this program includes the file directly).  Every expected answer restates the dispatch of
+// commit 4533235, twilight_amd/csrc/twl_align.hip (run_device, lines 549-629), read as the specification -- for the tile level, launch_mt of commit 610317e,
+// twilight_amd/csrc/twl_launch.inc.hip (lines 209-331); the line it restates is named.  Prints "OK <name>" / "FAIL <name>".
 #include <cstdio>
+#include <cstring>
 #include <string>
+#include <vector>
 #include "../twilight_amd/csrc/twl_policy.inc.hip"
 
 static int g_fail = 0;
 #define CHECK(name, cond) do { if (cond) printf("OK %s\n", name); else { printf("FAIL %s\n", name); ++g_fail; } } while (0)
 
-static Knobs knobs(int mt_wide = 1) { return Knobs{1024, 512, 70, mt_wide, 0, 0, 0, ProtMode::Auto, 448}; }      // the library's defaults (twl_knobs.inc.hip)
+static Knobs knobs(int mt_wide = 1) { return Knobs{1024, 512, 70, mt_wide, 0, 0, 0, ProtMode::Auto, 448, 256, 2, 1, 320, 40, 64, 96, 128}; }      // the library's defaults (twl_knobs.inc.hip)
 
 // The rungs a set of `count` pairs of summed length `sumLen` takes when it outgrows every window in turn, after an optional guard round on the first round.
 static std::string climb(const Ran &ran, int count, long long sumLen, bool guardFirst, int mt_wide = 1)
@@ -25,6 +28,33 @@ static std::string climb(const Ran &ran, int count, long long sumLen, bool guard
     return s + rung_name(next_rung(ran, at, RedoKind::Overflow, f, knobs(mt_wide)).rung);
 }
 static Ran nuc(Level start, bool leanMid = true, int mode = 2) { Ran r; r.start = start; r.leanMid = leanMid; r.mode = mode; return r; }
+
+// The plan and the job table of a tile-parallel level at marker 128, sequence capacity 300 (slots = 600 / 127 + 2 = 6: line 228), 12-word tile records (kMtRec, talco_nuc.hip.h).
+struct Tiles { TilePlan pl; std::vector<int32_t> jobs; };
+static Tiles tiles(const std::vector<int32_t> &order, const std::vector<int32_t> &len, const Knobs &k, bool wide = false, bool can_small = false, bool small_tiles = false)
+{
+    TileFacts f;
+    f.wide = wide; f.can_small = can_small; f.small_tiles = small_tiles;
+    f.n_run = (int)order.size(); f.marker = 128; f.seq_len = 300; f.rec_words = 12; f.order = order.data(); f.h_len = len.data();
+    Tiles t;
+    t.pl = plan_tile_level(f, k, t.jobs);
+    return t;
+}
+// n pairs of one tile each (R = Q = 1: line 241 stops at n = 1), in their own order
+static Tiles one_tile_pairs(int n, const Knobs &k, bool wide = false)
+{
+    std::vector<int32_t> order((size_t)n), len(2 * (size_t)n, 1);
+    for (int t = 0; t < n; ++t) order[t] = t;
+    return tiles(order, len, k, wide);
+}
+static std::string tile_name(int P, int mm, int tw, int trpl, int stitch_rpl, bool thr, bool smallT)
+{
+    TileFacts f; f.P = P; f.mm = mm; f.tw = tw; f.trpl = trpl; f.stitch_rpl = stitch_rpl;
+    TilePlan pl; pl.thr = thr; pl.smallT = smallT;
+    char s[160];      // (Device::kname)
+    tile_level_name(s, sizeof s, f, pl);
+    return s;
+}
 
 int main()
 {
@@ -122,5 +152,54 @@ int main()
     { // the memory as twl_plan_describe's argument carries it
       PassMemory a = memory_from_code(3), b = memory_from_code(1051), c = memory_from_code(100000 * 31 + 1000);
       CHECK("memory_from_code", a.wide_streak == 3 && b.wide_streak == 0 && b.last_wide_pct == 100 && b.wide_calls == 5 && c.small_for(1 << 30) == -1 && c.last_wide_pct == 0); }
+
+    // ---- plan_tile_level (launch_mt of commit 610317e, twl_launch.inc.hip) ----
+    { // the job table (232-247): scouts for every boundary s >= 1, then tiles for s >= 0, tile-major over `order`; the third word is the POSITION in `order` (231), not the pair id.
+      // pair 5 = (300, 300): 127 n - 1 <= 598 up to n = 4, so 5 tiles; pair 2 = (100, 150): 126 <= 248 but 253 > 248, so 2 (241)
+      std::vector<int32_t> len(12, 0); len[10] = len[11] = 300; len[4] = 100; len[5] = 150;
+      const Tiles t = tiles({5, 2}, len, k);
+      const std::vector<int32_t> want = {5,1,0, 2,1,1, 5,2,0, 5,3,0, 5,4,0,   5,0,0, 2,0,1, 5,1,0, 2,1,1, 5,2,0, 5,3,0, 5,4,0};
+      CHECK("tile_slots_segcap_pitch", t.pl.slots == 6 && t.pl.segcap == 272 && t.pl.sp_pitch == 608);      // 228-230
+      CHECK("tile_counts_per_pair", t.pl.T == std::vector<int>({5, 2}) && t.pl.maxT == 5 && t.pl.maxRQ == 600);      // 237-243, 294
+      CHECK("tile_jobs_tile_major_row_is_position", t.jobs == want && t.pl.nScout == 5 && t.pl.nTile == 7);      // 244-247
+      // 249-254, 257: chain [2][6][2] ints, records [2][6][12], segments [2][6][272] bytes, scout paths [2][608], 4 counters + [2][8] ints of frontier, 12 jobs x 3, anchors [2][6]
+      CHECK("tile_table_sizes", t.pl.chain_ints == 24 && t.pl.rec_ints == 144 && t.pl.seg_bytes == 3264 && t.pl.spath_ints == 1216 && t.pl.stat_bytes == 32 + 64 &&
+                                t.pl.jobs_ints == 36 && t.pl.anchor_ints == 12);
+      CHECK("tile_defaults_of_a_small_level", !t.pl.thr && !t.pl.smallT && t.pl.longScouts && t.pl.anchors && t.pl.rounds == 2 && t.pl.tb_groups == 0);      // 277, 216, 279, 256, 263
+      // the wide geometry (288-299): no anchors (256), the pair scout keeps (600 >> 3) + 2 groups of the longest pair (298), the shorter margin and lead (279-281)
+      const Tiles w = tiles({2, 5}, len, k, true);
+      CHECK("tile_wide_pair_scout", w.pl.tb_groups == 77 && !w.pl.anchors && w.pl.anchor_ints == 0 && !w.pl.thr && w.pl.marg == 40 && w.pl.lead2 == 96 &&
+                                    w.pl.T == std::vector<int>({2, 5}) && w.jobs[0] == 2 && w.jobs[2] == 0 && w.jobs[3] == 5 && w.jobs[5] == 1); }      // (the rows follow `order`: pair 2 is row 0 here)
+    { // the tile count's boundary (241: 127 n - 1 <= R + Q - 2): R + Q = 255 has 253 <= 253 and a third tile, 254 has not; R = Q = 1 is one tile and no scout
+      const Tiles a = tiles({0}, {128, 127}, k), b = tiles({0}, {127, 127}, k), c = tiles({0}, {1, 1}, k);
+      CHECK("tile_count_255", a.pl.T[0] == 3 && a.pl.nScout == 2 && a.pl.nTile == 3);
+      CHECK("tile_count_254", b.pl.T[0] == 2 && b.pl.nScout == 1 && b.pl.nTile == 2);
+      CHECK("tile_count_one_no_scout_no_anchors", c.pl.T[0] == 1 && c.pl.nScout == 0 && c.pl.nTile == 1 && k.mt_anchor == 1 && !c.pl.anchors && c.pl.anchor_ints == 0);      // 256: nScout > 0
+      Knobs k0 = k; k0.mt_anchor = 0;
+      CHECK("tile_anchor_knob_off", !tiles({0}, {128, 127}, k0).pl.anchors && a.pl.anchors); }
+    { // the throughput geometry (277: !WIDE && nTile > g_mt_thr_jobs, 256)
+      Knobs k0 = k; k0.mt_thr_jobs = 0;
+      CHECK("tile_thr_at_the_knob", !one_tile_pairs(256, k).pl.thr);
+      CHECK("tile_thr_above_the_knob", one_tile_pairs(257, k).pl.thr);
+      CHECK("tile_thr_knob_0", one_tile_pairs(1, k0).pl.thr);
+      CHECK("tile_thr_never_wide", !one_tile_pairs(257, k, true).pl.thr && !one_tile_pairs(1, k0, true).pl.thr); }
+    { // the longer scouts (279-281: !WIDE && nTile <= 2048 takes the _lat values 64 / 128, else 40 / 96)
+      const Tiles a = one_tile_pairs(2048, k), b = one_tile_pairs(2049, k), w = one_tile_pairs(2048, k, true);
+      CHECK("tile_long_scouts_2048", a.pl.longScouts && a.pl.marg == 64 && a.pl.lead2 == 128);
+      CHECK("tile_long_scouts_2049", !b.pl.longScouts && b.pl.marg == 40 && b.pl.lead2 == 96);
+      CHECK("tile_long_scouts_never_wide", !w.pl.longScouts && w.pl.marg == 40 && w.pl.lead2 == 96);
+      Knobs ke = k; ke.mt_marg = ke.mt_marg_lat = 50; ke.mt_lead2 = ke.mt_lead2_lat = 100;      // (TWL_KNOB_MT_MARGIN / TWL_KNOB_MT_LEAD2 set both kinds)
+      const Tiles c = one_tile_pairs(2048, ke), e = one_tile_pairs(2049, ke);
+      CHECK("tile_long_scouts_knob_set_both", c.pl.marg == 50 && e.pl.marg == 50 && c.pl.lead2 == 100 && e.pl.lead2 == 100); }
+    { // rounds (263: clamped to [1, 7]: 1 + 2 * 7 launches on 16 work counters)
+      Knobs k0 = k, k9 = k; k0.mt_rounds = 0; k9.mt_rounds = 9;
+      CHECK("tile_rounds_clamped", one_tile_pairs(1, k0).pl.rounds == 1 && one_tile_pairs(1, k).pl.rounds == 2 && one_tile_pairs(1, k9).pl.rounds == 7); }
+    { // tiles on the 512-row window (215-216: kCanSmall && small_tiles; kCanSmall is P == 6 && TW == 4 && !WIDE, so the protein instantiation passes false whatever the caller says)
+      CHECK("tile_small_needs_both", tiles({0}, {1, 1}, k, false, true, true).pl.smallT && !tiles({0}, {1, 1}, k, false, true, false).pl.smallT &&
+                                     !tiles({0}, {1, 1}, k, false, false, true).pl.smallT); }
+    // the kernel name (284-286), literally: throughput with small tiles (nucleotide, mode 5), throughput (protein 8 x 1, mode 4), and the 16-wave geometries (wide: 3 blocks per wave)
+    CHECK("tile_name_thr_small", tile_name(6, 5, 4, 3, 1, true, true) == "talco_lean_kernel<6, 4, 2, 5, 5, false, false, 2 / 1> + <6, 16, 1, 5, 1, false, false, 3> (tile-parallel: scouts, tiles, stitch)");
+    CHECK("tile_name_thr", tile_name(22, 4, 8, 1, 1, true, false) == "talco_lean_kernel<22, 8, 1, 4, 4, false, false, 2 / 1> + <22, 16, 1, 4, 1, false, false, 3> (tile-parallel: scouts, tiles, stitch)");
+    CHECK("tile_name_16_waves", tile_name(6, 2, 4, 3, 3, false, true) == "talco_lean_kernel<6, 16, 3, 2, 1, false, false, 2 / 1 / 3> (tile-parallel: scouts, tiles, stitch)");
     return g_fail ? 1 : 0;
 }

@@ -1,4 +1,4 @@
-"""Known-answer tests of the re-run ladder (next_rung) and of the pass memory (PassMemory) -- pure functions of twilight_amd/csrc/twl_policy.inc.hip,
+"""Known-answer tests of the re-run ladder (next_rung), of the pass memory (PassMemory) and of a tile-parallel level's plan (plan_tile_level) -- pure functions of twilight_amd/csrc/twl_policy.inc.hip,
 compiled by g++ into a small program (tests/policy_kats.cpp); runs without a GPU and without the library."""
 import os
 import subprocess
@@ -13,4 +13,4 @@ def test_ladder_and_pass_memory_known_answers(tmp_path):
     lines = [l for l in r.stdout.splitlines() if l.startswith(("OK", "FAIL"))]
     failed = [l for l in lines if l.startswith("FAIL")]
     assert not failed and r.returncode == 0, r.stdout + r.stderr
-    assert len(lines) >= 55
+    assert len(lines) >= 78

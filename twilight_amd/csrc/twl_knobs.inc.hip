@@ -20,3 +20,9 @@ int g_force_global = 0;             // twl_set_knob(TWL_KNOB_FORCE_GLOBAL): ever
 int g_assume_onehot_query = 0;       // twl_set_knob(TWL_KNOB_ASSUME_ONEHOT_QUERY): the host form too takes the one-letter-query kernels
 int g_leaf_step = 1;                 // twl_set_knob(TWL_KNOB_LEAF_STEP): 0 = leaf x leaf levels too run the general step (talco_lean_kernel, SP 0; tests hold the two to each other)
 int g_poison_tb = 0;                 // twl_set_knob(TWL_KNOB_POISON_TB): the traceback scratch is filled with 0xFF bytes in front of every DP launch (tests: a word whose store was wrongly skipped then reads as garbage, not as the zeros of a fresh allocation)
+// the knobs as the pure policy takes them (twl_policy.inc.hip)
+Knobs current_knobs()
+{
+    return Knobs{g_mt_max_pairs, g_mt_min_marker, g_mt_tail_pct, g_mt_wide, g_assume_onehot_query, g_no_spec, g_thr_small, (ProtMode)g_prot_mode, g_prot_corridor,
+                 g_mt_thr_jobs, g_mt_rounds, g_mt_anchor, g_mt_lead, g_mt_marg, g_mt_marg_lat, g_mt_lead2, g_mt_lead2_lat};
+}

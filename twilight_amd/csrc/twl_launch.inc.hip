@@ -1,30 +1,55 @@
 // twilight_amd/csrc/twl_launch.inc.hip -- one function per kernel family that sizes the scratch, fills the kernel arguments and launches: round-1 kernels, the global-memory kernel, the lean kernels, the tile-parallel launches of a level.
 // Included by twl_align.hip (one translation unit: it shares that file's Device bookkeeping, error string and fill queue).
 
+// Traceback words of a workgroup: the groups of 8 anti-diagonals up to the marker, a window of rows each.
 template <class CfgT>
 size_t tb_words_for(int marker) { return ((size_t)(marker >> 3) + 1) * (size_t)CfgT::WINDOW; }
+// ... `words` of them for each of `grid` workgroups in `b`, poisoned when the knob asks (tests: see g_poison_tb)
+int ensure_tb(Buf &b, hipStream_t st, size_t words, int grid)
+{
+    const size_t bytes = words * sizeof(uint32_t) * (size_t)grid;
+    if (const int rc = b.ensure(bytes)) return rc;
+    if (g_poison_tb) HIP_TRY(hipMemsetAsync(b.p, 0xFF, bytes, st));
+    return TWL_OK;
+}
+// Resident workgroups per CU of one kernel instantiation, queried once (the static is one per instantiation; device threads may race to fill it: same value).
+template <auto Kernel, int THREADS>
+int resident_per_cu(int *out)
+{
+    static std::atomic<int> cached{0};
+    if (cached.load() == 0) {
+        int nb = 0;
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, Kernel, THREADS, 0));
+        cached.store(std::max(1, nb));
+    }
+    *out = cached.load();
+    return TWL_OK;
+}
+// What the lean kernels' arguments take over from the call's; the caller adds the traceback scratch, the items, the work counter and what is its own.
+twl::NArgs lean_args(const Device *d, const twl::KArgs &base)
+{
+    twl::NArgs a{};
+    a.cols = base.cols; a.len = base.len; a.num = base.num; a.aln = base.aln; a.aln_len = base.aln_len; a.err = base.err;
+    a.cells = base.cells; a.seq_len = base.seq_len; a.n_pairs_total = base.n_pairs_total;
+    a.step_slack = base.step_slack; a.gap_open = base.gap_open; a.gap_extend = base.gap_extend; a.gap_char = base.gap_char; a.gc_zero = base.gc_zero;
+    a.xdrop = base.xdrop; a.flen = base.flen; a.marker = base.marker;
+    for (int t = 0; t < 25; ++t) a.M[t] = base.M[t];
+    a.M24 = (const float *)d->m24.p; a.sim = base.sim; a.sim_off = base.sim_off;
+    return a;
+}
 
 template <int P, int W, int RPL, bool PRE, bool REFLDS, bool QREG = true, int MINW = 1, int MM = 0>
 int launch_dp(Device *d, hipStream_t st, const twl::KArgs &base, const int32_t *d_items, int n_items, int blocks_per_cu, int *grid_out,
               int *window_out = nullptr)
 {
     using CfgT = twl::Cfg<P, W, RPL, PRE, REFLDS, QREG>;
-    if (blocks_per_cu <= 0) {
-        static std::atomic<int> cached{0};      // one value per template instantiation (device threads may race to fill it: same value)
-        if (cached.load() == 0) {
-            int nb = 0;
-            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (twl::talco_kernel<P, W, RPL, PRE, REFLDS, QREG, MINW, MM>), CfgT::THREADS, 0));
-            cached.store(std::max(1, nb));
-        }
-        blocks_per_cu = cached.load();
-    }
+    int rc;
+    if (blocks_per_cu <= 0 && (rc = resident_per_cu<twl::talco_kernel<P, W, RPL, PRE, REFLDS, QREG, MINW, MM>, CfgT::THREADS>(&blocks_per_cu))) return rc;
     if (window_out) *window_out = CfgT::WINDOW;
     int grid = std::min(n_items, d->num_cu * std::max(1, blocks_per_cu));
     if (grid < 1) grid = 1;
     const size_t tbw = tb_words_for<CfgT>(base.marker);
-    int rc = d->tb.ensure(tbw * sizeof(uint32_t) * (size_t)grid);
-    if (rc) return rc;
-    if (g_poison_tb) HIP_TRY(hipMemsetAsync(d->tb.p, 0xFF, tbw * sizeof(uint32_t) * (size_t)grid, st));
+    if ((rc = ensure_tb(d->tb, st, tbw, grid))) return rc;
     twl::KArgs a = base;
     a.tb = (uint32_t *)d->tb.p;
     a.tb_words = (int32_t)tbw;
@@ -73,9 +98,8 @@ int launch_global(Device *d, hipStream_t st, const twl::KArgs &base, const int32
     grid = std::min(grid, d->num_cu);
     // a buffer of its own, handed back after the stage (run_device: release_global_scratch): d->tb lives until twl_shutdown and a single retry of the deferred
     // pass would otherwise pin several GiB next to the resident store for the rest of the run
-    int rc = d->gtb.ensure(words * sizeof(uint32_t) * (size_t)grid);
+    const int rc = ensure_tb(d->gtb, st, words, grid);
     if (rc) return rc;
-    if (g_poison_tb) HIP_TRY(hipMemsetAsync(d->gtb.p, 0xFF, words * sizeof(uint32_t) * (size_t)grid, st));
     twl::GArgs g;
     g.k = base;
     g.k.tb = (uint32_t *)d->gtb.p;
@@ -99,13 +123,8 @@ template <int P, int W, int RPL, int MM, int MINW, bool SPEC = false, bool DUMP 
 int launch_lean(Device *d, hipStream_t st, const twl::KArgs &base, const int32_t *d_items, int n_items, int *grid_out, int *window_out)
 {
     using CfgT = twl::NCfg<W, RPL>;
-    static std::atomic<int> cached{0};      // one value per template instantiation
-    if (cached.load() == 0) {
-        int nb = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (twl::talco_lean_kernel<P, W, RPL, MM, MINW, SPEC, DUMP, 0, SP>), CfgT::THREADS, 0));
-        cached.store(std::max(1, nb));
-    }
-    int blocks_per_cu = cached.load();
+    int rc, blocks_per_cu = 0;
+    if ((rc = resident_per_cu<twl::talco_lean_kernel<P, W, RPL, MM, MINW, SPEC, DUMP, 0, SP>, CfgT::THREADS>(&blocks_per_cu))) return rc;
     if (window_out) *window_out = CfgT::WINDOW;
     int grid = std::min(n_items, d->num_cu * blocks_per_cu);
     if (grid < 1) grid = 1;
@@ -113,18 +132,10 @@ int launch_lean(Device *d, hipStream_t st, const twl::KArgs &base, const int32_t
         grid = 2 * n_items;
         if (grid > d->num_cu * blocks_per_cu) { g_err = "speculative launch larger than the device"; return TWL_ERR_BAD_ARGUMENT; }
     }
-    const size_t tbw = ((size_t)(base.marker >> 3) + 1) * (size_t)CfgT::WINDOW;
-    int rc = d->tb.ensure(tbw * sizeof(uint32_t) * (size_t)grid);
-    if (rc) return rc;
-    if (g_poison_tb) HIP_TRY(hipMemsetAsync(d->tb.p, 0xFF, tbw * sizeof(uint32_t) * (size_t)grid, st));
-    twl::NArgs a{};
-    a.cols = base.cols; a.len = base.len; a.num = base.num; a.aln = base.aln; a.aln_len = base.aln_len; a.err = base.err;
-    a.cells = base.cells; a.tb = (uint32_t *)d->tb.p; a.queue = base.queue; a.items = d_items; a.n_items = n_items;
-    a.seq_len = base.seq_len; a.tb_words = (int32_t)tbw; a.dbg = base.dbg; a.n_pairs_total = base.n_pairs_total;
-    a.step_slack = base.step_slack; a.gap_open = base.gap_open; a.gap_extend = base.gap_extend; a.gap_char = base.gap_char; a.gc_zero = base.gc_zero;
-    a.xdrop = base.xdrop; a.flen = base.flen; a.marker = base.marker;
-    for (int t = 0; t < 25; ++t) a.M[t] = base.M[t];
-    a.M24 = (const float *)d->m24.p; a.sim = base.sim; a.sim_off = base.sim_off;
+    const size_t tbw = tb_words_for<CfgT>(base.marker);
+    if ((rc = ensure_tb(d->tb, st, tbw, grid))) return rc;
+    twl::NArgs a = lean_args(d, base);
+    a.tb = (uint32_t *)d->tb.p; a.tb_words = (int32_t)tbw; a.queue = base.queue; a.items = d_items; a.n_items = n_items; a.dbg = base.dbg;
     FILL_TRY(queue_fill(d, st, d->queue.p, sizeof(int32_t), 0));
     if (SPEC) {
         if ((rc = d->team.ensure((size_t)n_items * twl::kTeamWords * sizeof(unsigned long long)))) return rc;
@@ -153,25 +164,18 @@ int launch_lean(Device *d, hipStream_t st, const twl::KArgs &base, const int32_t
     return TWL_OK;
 }
 
-constexpr int kMtMaxRounds = 7, kMtCounters = 16;      // 1 + 2 * rounds launches, each with its own work counter (the count is clamped wherever it is set)
 // One launch of a tile-parallel kernel (MT 1 tiles / 2 scouts / 3 stitch) of geometry <W, RPL>; the caller has filled the NArgs.
 template <int P, int W, int RPL, int MM, int MINW, int MT, int SP = 0>
 int launch_mt_kernel(Device *d, hipStream_t st, twl::NArgs a, int n_items, int *grid_out = nullptr, size_t tb_groups = 0)
 {
     using CfgT = twl::NCfg<W, RPL>;
-    static std::atomic<int> cached{0};
-    if (cached.load() == 0) {
-        int nb = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (twl::talco_lean_kernel<P, W, RPL, MM, MINW, false, false, MT, SP>), CfgT::THREADS, 0));
-        cached.store(std::max(1, nb));
-    }
-    int grid = std::max(1, std::min(n_items, d->num_cu * cached.load()));
-    // traceback words of a workgroup: the groups of 8 anti-diagonals up to the marker, or (pair scouts, MT 4) of a whole pair
-    const size_t tbw = (tb_groups ? tb_groups : (size_t)(a.marker >> 3) + 1) * (size_t)CfgT::WINDOW;
+    int rc, blocks_per_cu = 0;
+    if ((rc = resident_per_cu<twl::talco_lean_kernel<P, W, RPL, MM, MINW, false, false, MT, SP>, CfgT::THREADS>(&blocks_per_cu))) return rc;
+    int grid = std::max(1, std::min(n_items, d->num_cu * blocks_per_cu));
+    // traceback words of a workgroup: up to the marker, or (pair scouts, MT 4) the tb_groups groups of a whole pair
+    const size_t tbw = tb_groups ? tb_groups * (size_t)CfgT::WINDOW : tb_words_for<CfgT>(a.marker);
     if (tb_groups) grid = (int)std::max<size_t>(1, std::min<size_t>((size_t)grid, ((size_t)8 << 30) / (tbw * sizeof(uint32_t))));      // (at most 8 GB of them: fewer workgroups take the pairs in turn)
-    int rc = d->tb.ensure(tbw * sizeof(uint32_t) * (size_t)grid);
-    if (rc) return rc;
-    if (g_poison_tb) HIP_TRY(hipMemsetAsync(d->tb.p, 0xFF, tbw * sizeof(uint32_t) * (size_t)grid, st));
+    if ((rc = ensure_tb(d->tb, st, tbw, grid))) return rc;
     a.tb = (uint32_t *)d->tb.p; a.tb_words = (int32_t)tbw; a.n_items = n_items;
     // (every launch of a tile-parallel level has its own work counter: launch_mt zeroed the 16 of them in one go)
     a.queue = (int32_t *)d->queue.p + (d->mt_launch++ % kMtCounters);
@@ -201,6 +205,27 @@ int launch_mt_thr(Device *d, hipStream_t st, const twl::NArgs &a, int n_items, i
     return launch_mt_kernel<6, W, RPL, MM, MINW, MT>(d, st, a, n_items, grid_out);
 }
 
+// The tables of a tile-parallel level as its plan sizes them, the upload of its jobs (`jobs` outlives the call: Device::mt_jobs_host) and the fills, queued in front of its first kernel.
+int prepare_mt_tables(Device *d, hipStream_t st, const TilePlan &pl, const std::vector<int32_t> &jobs)
+{
+    int rc;
+    if ((rc = d->mt_chain.ensure(pl.chain_ints * sizeof(int32_t)))) return rc;
+    if ((rc = d->mt_rec.ensure(pl.rec_ints * sizeof(int32_t)))) return rc;
+    if ((rc = d->mt_seg.ensure(pl.seg_bytes))) return rc;
+    if ((rc = d->mt_spath.ensure(pl.spath_ints * sizeof(int32_t)))) return rc;
+    if ((rc = d->mt_stat.ensure(pl.stat_bytes))) return rc;
+    if ((rc = d->mt_jobs.ensure(pl.jobs_ints * sizeof(int32_t)))) return rc;
+    if (pl.anchors && (rc = d->mt_anchor.ensure(pl.anchor_ints * sizeof(int32_t)))) return rc;
+    HIP_TRY(hipMemcpyAsync(d->mt_jobs.p, jobs.data(), pl.jobs_ints * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    FILL_TRY(queue_fill(d, st, d->mt_rec.p, pl.rec_ints * sizeof(int32_t), 0));
+    FILL_TRY(queue_fill(d, st, d->mt_spath.p, pl.spath_ints * sizeof(int32_t), 0xFE));
+    FILL_TRY(queue_fill(d, st, d->mt_stat.p, pl.stat_bytes, 0));
+    if (pl.anchors) FILL_TRY(queue_fill(d, st, d->mt_anchor.p, pl.anchor_ints * sizeof(int32_t), 0xFF));
+    FILL_TRY(queue_fill(d, st, d->queue.p, kMtCounters * sizeof(int32_t), 0));      // one work counter per launch: scouts + rounds x (tiles, stitch); launch_mt_kernel hands them out
+    d->mt_launch = 0;
+    return TWL_OK;
+}
+
 // Tile-parallel alignment of a level with few pairs (talco_nuc.hip.h, MT kernels): scouts, then rounds of chain -> tiles -> stitch, on `st`.
 // `order` = the pairs that run, h_len their lengths on the host.  Scouts and tiles run on the 16-wave geometry (one workgroup per CU, the
 // shortest diagonal step) while they fit the device at once (one workgroup per CU), on the throughput geometry (8 waves x 2 blocks, two per CU) beyond.
@@ -209,11 +234,7 @@ template <int P, int MM, int TRPL, bool WIDE = false, int TW = 8>      // TW x T
 int launch_mt(Device *d, hipStream_t st, const twl::KArgs &base, const int32_t *d_items, const std::vector<int32_t> &order, int n_run,
               const int32_t *h_len, int *grid_out, int *window_out, bool small_tiles = false, int sp = 0)
 {
-    // small_tiles (nucleotide, throughput geometry): the tile jobs too run on 4 waves x 2 blocks, five workgroups per CU -- the earlier levels of this pass
-    // fitted the 512-row window (plan_nucleotide, small).  A tile that outgrows it leaves a failed record of a window narrower than the stitch launch's, which
-    // the stitch launch does not adopt: it computes that tile in line (run_device counts them and takes the pass off the small window when they are many).
     constexpr bool kCanSmall = (P == 6 && TW == 4 && !WIDE);
-    const bool smallT = kCanSmall && small_tiles;
     // WIDE (nucleotide): the tiles and the stitch launch on 16 waves x 3 blocks, a 3072-row window -- for the pairs whose band outgrew the
     // 1024-row window of the fast geometries.  Until round 4 those ran their ~20 tiles one after the other on the 2048- and 4608-row kernels
     // (0.2-0.6 s per 10 kbp pair); their tiles are as independent as anybody's.  The scouts keep the narrow geometry: a scout's band opens
@@ -224,109 +245,63 @@ int launch_mt(Device *d, hipStream_t st, const twl::KArgs &base, const int32_t *
     constexpr int SW = 16, SR = WIDE ? 3 : 1;       // geometry of the stitch launch and of tiles while they fit the device at once
 #endif
     if (window_out) *window_out = twl::NCfg<SW, SR>::WINDOW;
-    const int marker = base.marker;
-    const int slots = (2 * base.seq_len) / (marker - 1) + 2;
-    const int segcap = 2 * marker + 16;
-    const int sp_pitch = 2 * base.seq_len + 8;
-    const size_t np = (size_t)n_run;               // the tables are indexed by the position of a pair in `order` (not by pair id)
-    // jobs {pair, slot, row}: scouts for every tile boundary t >= 1 that exists, tiles for t >= 0 (tile-major, so that the tiles of a pair spread over the launch)
-    std::vector<int32_t> &jobs = d->mt_jobs_host;       // scouts first, then tiles (kept with the device: the upload below is asynchronous)
-    jobs.clear();
-    int maxT = 0;
-    std::vector<int> T((size_t)n_run);
-    for (int t = 0; t < n_run; ++t) {
-        const int pr = order[t];
-        const long long RQ = (long long)h_len[2 * pr] + h_len[2 * pr + 1];
-        int n = 1;
-        while (n < slots && (long long)(marker - 1) * n - 1 <= RQ - 2) ++n;
-        T[t] = n; maxT = std::max(maxT, n);
-    }
-    for (int s = 1; s < maxT; ++s) for (int t = 0; t < n_run; ++t) if (s < T[t]) { jobs.push_back(order[t]); jobs.push_back(s); jobs.push_back(t); }
-    const int nScout = (int)(jobs.size() / 3);
-    for (int s = 0; s < maxT; ++s) for (int t = 0; t < n_run; ++t) if (s < T[t]) { jobs.push_back(order[t]); jobs.push_back(s); jobs.push_back(t); }
-    const int nTile = (int)(jobs.size() / 3) - nScout;
+    TileFacts f;
+    f.P = P; f.mm = MM; f.tw = TW; f.trpl = TRPL; f.stitch_rpl = SR; f.wide = WIDE; f.can_small = kCanSmall; f.small_tiles = small_tiles;
+    f.n_run = n_run; f.marker = base.marker; f.seq_len = base.seq_len; f.rec_words = twl::kMtRec; f.order = order.data(); f.h_len = h_len;
+    const Knobs k = current_knobs();
+    const TilePlan pl = plan_tile_level(f, k, d->mt_jobs_host);       // (the jobs are kept with the device: their upload is asynchronous)
     int rc;
-    if ((rc = d->mt_chain.ensure(np * slots * 2 * sizeof(int32_t)))) return rc;
-    if ((rc = d->mt_rec.ensure(np * slots * twl::kMtRec * sizeof(int32_t)))) return rc;
-    if ((rc = d->mt_seg.ensure(np * slots * (size_t)segcap))) return rc;
-    if ((rc = d->mt_spath.ensure(np * (size_t)sp_pitch * sizeof(int32_t)))) return rc;
-    if ((rc = d->mt_stat.ensure(4 * sizeof(unsigned long long) + np * 8 * sizeof(int32_t)))) return rc;      // counters, then the per-pair frontier
-    if ((rc = d->mt_jobs.ensure(jobs.size() * sizeof(int32_t)))) return rc;
-    // scouts of the narrow geometries start from an anchored cell where the profiles give one (talco_nuc.hip.h, mt_anchor_kernel)
-    const bool anchors = !WIDE && g_mt_anchor && nScout > 0;
-    if (anchors && (rc = d->mt_anchor.ensure(np * slots * sizeof(int32_t)))) return rc;
-    HIP_TRY(hipMemcpyAsync(d->mt_jobs.p, jobs.data(), jobs.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    FILL_TRY(queue_fill(d, st, d->mt_rec.p, np * slots * twl::kMtRec * sizeof(int32_t), 0));
-    FILL_TRY(queue_fill(d, st, d->mt_spath.p, np * (size_t)sp_pitch * sizeof(int32_t), 0xFE));
-    FILL_TRY(queue_fill(d, st, d->mt_stat.p, 4 * sizeof(unsigned long long) + np * 8 * sizeof(int32_t), 0));
-    if (anchors) FILL_TRY(queue_fill(d, st, d->mt_anchor.p, np * slots * sizeof(int32_t), 0xFF));
-    const int rounds = std::max(1, std::min(g_mt_rounds, kMtMaxRounds));
-    FILL_TRY(queue_fill(d, st, d->queue.p, kMtCounters * sizeof(int32_t), 0));      // one work counter per launch: scouts + rounds x (tiles, stitch)
-    d->mt_launch = 0;
-    twl::NArgs a{};
-    a.cols = base.cols; a.len = base.len; a.num = base.num; a.aln = base.aln; a.aln_len = base.aln_len; a.err = base.err;
-    a.cells = base.cells; a.queue = base.queue; a.items = d_items;
-    a.seq_len = base.seq_len; a.dbg = nullptr; a.n_pairs_total = base.n_pairs_total;
-    a.step_slack = base.step_slack; a.gap_open = base.gap_open; a.gap_extend = base.gap_extend; a.gap_char = base.gap_char; a.gc_zero = base.gc_zero;
-    a.xdrop = base.xdrop; a.flen = base.flen; a.marker = base.marker;
-    for (int t = 0; t < 25; ++t) a.M[t] = base.M[t];
-    a.M24 = (const float *)d->m24.p; a.sim = base.sim; a.sim_off = base.sim_off;
+    if ((rc = prepare_mt_tables(d, st, pl, d->mt_jobs_host))) return rc;
+    twl::NArgs a = lean_args(d, base);
+    a.items = d_items;
     a.mt_chain = (int32_t *)d->mt_chain.p; a.mt_rec = (int32_t *)d->mt_rec.p; a.mt_seg = (int8_t *)d->mt_seg.p; a.mt_spath = (int32_t *)d->mt_spath.p;
     a.mt_stat = (unsigned long long *)d->mt_stat.p;
     a.mt_front = (int32_t *)((unsigned long long *)d->mt_stat.p + 4);
-    const bool thr = !WIDE && nTile > g_mt_thr_jobs;
-    // (see twl_knobs.inc.hip: longer scouts where the tile jobs are at most a round or two of the device's workgroups and a missed start a second round that lasts as long as the first)
-    const bool longScouts = !WIDE && nTile <= 2048;
-    const int lead2 = longScouts ? g_mt_lead2_lat : g_mt_lead2;
-    a.mt_slots = slots; a.mt_segcap = segcap; a.mt_sp_pitch = sp_pitch; a.mt_lead = g_mt_lead; a.mt_marg = longScouts ? g_mt_marg_lat : g_mt_marg;
-    TRACE("launch mt pairs=%d scouts=%d tiles=%d slots=%d geometry=%s", n_run, nScout, nTile, slots, WIDE ? "16x3 (wide)" : (thr ? "throughput geometry" : "16x1"));
-    if (!d->kname[0]) {
-        if (thr && smallT) snprintf(d->kname, sizeof d->kname, "talco_lean_kernel<%d, 4, 2, %d, 5, false, false, 2 / 1> + <%d, 16, 1, %d, 1, false, false, 3> (tile-parallel: scouts, tiles, stitch)", P, MM, P, MM);
-        else if (thr) snprintf(d->kname, sizeof d->kname, "talco_lean_kernel<%d, %d, %d, %d, 4, false, false, 2 / 1> + <%d, 16, 1, %d, 1, false, false, 3> (tile-parallel: scouts, tiles, stitch)", P, TW, TRPL, MM, P, MM);
-        else snprintf(d->kname, sizeof d->kname, "talco_lean_kernel<%d, 16, %d, %d, 1, false, false, 2 / 1 / 3> (tile-parallel: scouts, tiles, stitch)", P, SR, MM);
-    }
-    if (WIDE) {
+    a.mt_slots = pl.slots; a.mt_segcap = pl.segcap; a.mt_sp_pitch = pl.sp_pitch; a.mt_lead = k.mt_lead; a.mt_marg = pl.marg;
+    TRACE("launch mt pairs=%d scouts=%d tiles=%d slots=%d geometry=%s", n_run, pl.nScout, pl.nTile, pl.slots, WIDE ? "16x3 (wide)" : (pl.thr ? "throughput geometry" : "16x1"));
+    if (!d->kname[0]) tile_level_name(d->kname, sizeof d->kname, f, pl);
+    if constexpr (WIDE) {
         // pairs that outgrew the fast window are, more often than not, pairs whose tiles converge late or never (diffuse profiles): a tile then runs
         // to the end of the pair and the next one starts where the path from the END cell crosses the marker diagonal -- nothing a scout that
         // starts 320 diagonals ahead can know.  One workgroup per pair runs the whole DP once with every traceback word kept (MT 4) and leaves the
         // global path's crossing of every anti-diagonal; its suffixes are what the tiles' own paths follow.
-        int maxRQ = 0;
-        for (int t = 0; t < n_run; ++t) maxRQ = std::max(maxRQ, h_len[2 * order[t]] + h_len[2 * order[t] + 1]);
         if constexpr (P == 6) {
             twl::NArgs as = a;
             as.xdrop = (int32_t)((long long)a.xdrop * g_scout_xdrop_pct / 100);
-            if ((rc = launch_mt_kernel<P, SW, SR, MM, 1, 4>(d, st, as, n_run, nullptr, (size_t)(maxRQ >> 3) + 2))) return rc;
+            if ((rc = launch_mt_kernel<P, SW, SR, MM, 1, 4>(d, st, as, n_run, nullptr, pl.tb_groups))) return rc;
         }
-    } else if (nScout > 0) {
+    } else if (pl.nScout > 0) {
         a.mt_jobs = (const int32_t *)d->mt_jobs.p;
-        if (anchors) {
+        if (pl.anchors) {
             FILL_TRY(flush_fills(d, st));
-            hipLaunchKernelGGL(twl::mt_anchor_kernel<P>, dim3(nScout), dim3(256), 0, st, base.cols, base.len, base.seq_len, a.mt_jobs, nScout, (int32_t *)d->mt_anchor.p, slots, marker, lead2);
+            hipLaunchKernelGGL(twl::mt_anchor_kernel<P>, dim3(pl.nScout), dim3(256), 0, st, base.cols, base.len, base.seq_len, a.mt_jobs, pl.nScout, (int32_t *)d->mt_anchor.p, pl.slots, base.marker, pl.lead2);
             HIP_TRY(hipGetLastError());
-            a.mt_anchor = (const int32_t *)d->mt_anchor.p; a.mt_lead2 = lead2;
+            a.mt_anchor = (const int32_t *)d->mt_anchor.p; a.mt_lead2 = pl.lead2;
         }
-        const bool thrS = WIDE ? nScout > g_mt_thr_jobs : thr;
-        // (nucleotide scouts of the throughput geometry run ~330 diagonals from one cell: their band opens by a row per diagonal and cannot outgrow 449 rows, so
-        //  they take the 512-row window -- 4 waves x 2 blocks, FIVE workgroups per CU, see plan_nucleotide -- whatever the tiles need)
-        if constexpr (P == 6 && TW == 4 && !WIDE) rc = thrS ? launch_mt_thr<4, 2, MM, 5, 2>(d, st, a, nScout, nullptr, sp) : launch_mt_kernel<P, SW, SR, MM, 1, 2>(d, st, a, nScout);
-        else rc = thrS ? launch_mt_kernel<P, TW, TRPL, MM, 4, 2>(d, st, a, nScout) : launch_mt_kernel<P, WIDE ? 16 : SW, WIDE ? 1 : SR, MM, 1, 2>(d, st, a, nScout);
+        // Nucleotide scouts of the throughput geometry take the 512-row window (4 waves x 2 blocks, FIVE workgroups per CU, see plan_nucleotide) whatever the
+        // tiles need.  The scout of boundary `slot` runs min(slot + 2 + marg + lead, kMaxMarker) anti-diagonals from one cell (talco_lean_kernel, MT 2: its marker is
+        // spHi + mt_marg - scoutD0, spHi - spLo = slot + 2, lead = mt_lead2 when it is anchored and mt_lead when not), and the premise is that its band opens by
+        // about a row per diagonal.  With the knobs' defaults that is at most 320 + 40 + 2 + slot = 362 + slot rows, and 320 + 64 + 2 + slot = 386 + slot with the
+        // longer margin of the levels of at most 2048 tile jobs: within 512 rows up to boundary 126 (pairs of ~129 000 columns at marker 1024), past it beyond.
+        // A scout that outgrows the window predicts nothing, and the tile it was to start costs a tile in line or a second round.
+        if constexpr (kCanSmall) rc = pl.thr ? launch_mt_thr<4, 2, MM, 5, 2>(d, st, a, pl.nScout, nullptr, sp) : launch_mt_kernel<P, SW, SR, MM, 1, 2>(d, st, a, pl.nScout);
+        else rc = pl.thr ? launch_mt_kernel<P, TW, TRPL, MM, 4, 2>(d, st, a, pl.nScout) : launch_mt_kernel<P, SW, SR, MM, 1, 2>(d, st, a, pl.nScout);
         if (rc) return rc;
     }
-    for (int r = 0; r < rounds; ++r) {
+    for (int r = 0; r < pl.rounds; ++r) {
         FILL_TRY(flush_fills(d, st));
-        hipLaunchKernelGGL(twl::mt_chain_kernel, dim3((n_run + 63) / 64), dim3(64), 0, st, (const int32_t *)d->mt_spath.p, sp_pitch, base.len, d_items, n_run,
-                           (int32_t *)d->mt_chain.p, slots, marker, g_mt_perturb, (const int32_t *)a.mt_front);
+        hipLaunchKernelGGL(twl::mt_chain_kernel, dim3((n_run + 63) / 64), dim3(64), 0, st, (const int32_t *)d->mt_spath.p, pl.sp_pitch, base.len, d_items, n_run,
+                           (int32_t *)d->mt_chain.p, pl.slots, base.marker, g_mt_perturb, (const int32_t *)a.mt_front);
         HIP_TRY(hipGetLastError());
-        a.mt_jobs = (const int32_t *)d->mt_jobs.p + 3 * (size_t)nScout;
-        if constexpr (kCanSmall) rc = thr ? (smallT ? launch_mt_thr<4, 2, MM, 5, 1>(d, st, a, nTile, grid_out, sp) : launch_mt_thr<TW, TRPL, MM, 4, 1>(d, st, a, nTile, grid_out, sp))
-                                          : launch_mt_kernel<P, SW, SR, MM, 1, 1>(d, st, a, nTile, grid_out);
-        else rc = thr ? launch_mt_kernel<P, TW, TRPL, MM, 4, 1>(d, st, a, nTile, grid_out) : launch_mt_kernel<P, SW, SR, MM, 1, 1>(d, st, a, nTile, grid_out);
+        a.mt_jobs = (const int32_t *)d->mt_jobs.p + 3 * (size_t)pl.nScout;
+        if constexpr (kCanSmall) rc = pl.thr ? (pl.smallT ? launch_mt_thr<4, 2, MM, 5, 1>(d, st, a, pl.nTile, grid_out, sp) : launch_mt_thr<TW, TRPL, MM, 4, 1>(d, st, a, pl.nTile, grid_out, sp))
+                                             : launch_mt_kernel<P, SW, SR, MM, 1, 1>(d, st, a, pl.nTile, grid_out);
+        else rc = pl.thr ? launch_mt_kernel<P, TW, TRPL, MM, 4, 1>(d, st, a, pl.nTile, grid_out) : launch_mt_kernel<P, SW, SR, MM, 1, 1>(d, st, a, pl.nTile, grid_out);
         if (rc) return rc;
         a.mt_jobs = nullptr;
-        a.mt_inline = (r == rounds - 1) ? 1 : 0;
+        a.mt_inline = (r == pl.rounds - 1) ? 1 : 0;
         a.dbg = a.mt_inline ? base.dbg : nullptr;
         if ((rc = launch_mt_kernel<P, SW, SR, MM, 1, 3>(d, st, a, n_run))) return rc;
     }
     return TWL_OK;
 }
-

@@ -1,14 +1,20 @@
 // twilight_amd/csrc/twl_policy.inc.hip -- the launch policy of a DP call as PURE functions of the call's facts: the first launch (plan_nucleotide, plan_protein), the rung a set of
-// outgrown pairs takes next (next_rung) and what a device remembers of a pass (PassMemory).  No HIP call in this file: twl_plan_describe prints the plans without a device
-// (tests/test_policy_cpu.py), tests/policy_kats.cpp includes the file directly for the ladder and the memory.  Included by twl_align.hip (one translation unit).
+// outgrown pairs takes next (next_rung), what a device remembers of a pass (PassMemory) and what a tile-parallel level launches on which tables (plan_tile_level).  No HIP call
+// in this file: twl_plan_describe prints the plans without a device (tests/test_policy_cpu.py), tests/policy_kats.cpp includes the file directly for the ladder, the memory and
+// the tile level.  Included by twl_align.hip (one translation unit).
 #include <algorithm>
 #include <climits>
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
+#include <vector>
 
 // TWL_KNOB_PROT_MODE: auto | dense | sparse | presim | r1 (round-1 kernels) | lean_sparse | lean_presim
 enum class ProtMode { Auto, Dense, Sparse, Presim, R1, LeanSparse, LeanPresim };
-struct Knobs { int mt_max_pairs, mt_min_marker, mt_tail_pct, mt_wide, assume_onehot_query, no_spec, thr_small; ProtMode prot_mode; int prot_corridor; };
+struct Knobs {
+    int mt_max_pairs, mt_min_marker, mt_tail_pct, mt_wide, assume_onehot_query, no_spec, thr_small; ProtMode prot_mode; int prot_corridor;
+    int mt_thr_jobs, mt_rounds, mt_anchor, mt_lead, mt_marg, mt_marg_lat, mt_lead2, mt_lead2_lat;      // of a tile-parallel level (plan_tile_level)
+};
 // fast_div's guard (talco_nuc.hip.h): non-zero scores within [2^-10, 2^10]; anything else takes the IEEE-division kernel
 inline bool fast_div_in_range(const float *M, int n, float gap_char)
 {
@@ -202,6 +208,82 @@ const char *nuc_first_name(NucFirst f)
     }
 }
 
+// ---- a tile-parallel level (launch_mt): its jobs, the sizes of its tables, the geometry class of its launches ----
+constexpr int kMtMaxRounds = 7, kMtCounters = 16;      // 1 + 2 * rounds launches, each with its own work counter (the count is clamped wherever it is set)
+static_assert(1 + 2 * kMtMaxRounds <= kMtCounters, "scouts + rounds x (tiles, stitch): every launch of a tile-parallel level has a work counter of its own");
+struct TileFacts {
+    int P = 6, mm = 2, tw = 8, trpl = 1, stitch_rpl = 1;      // launch_mt's template arguments and the 64-row blocks per wave of its stitch launch, as the kernel name carries them
+    bool wide = false;                    // the 3072-row geometry (launch_mt, WIDE)
+    bool can_small = false;               // the instantiation has the 512-row throughput geometry (nucleotide, 4-wave throughput geometry, not wide) ...
+    bool small_tiles = false;             // ... and the earlier levels of this pass fitted it
+    int n_run = 0, marker = 0, seq_len = 0;
+    int rec_words = 0;                    // words of a tile's record (talco_nuc.hip.h, kMtRec)
+    const int32_t *order = nullptr;       // the pairs that run
+    const int32_t *h_len = nullptr;       // [pair][2]
+};
+struct TilePlan {
+    int slots = 0, segcap = 0, sp_pitch = 0;      // tile boundaries of the longest pair the call may hold, bytes of a tile's path segment, words of a pair's scout path
+    std::vector<int> T;                   // tiles of every pair, by its position in `order`
+    int maxT = 0, nScout = 0, nTile = 0;  // jobs {pair, slot, row}: nScout scouts, then nTile tiles
+    long long maxRQ = 0;                  // R + Q of the longest pair
+    size_t chain_ints = 0, rec_ints = 0, seg_bytes = 0, spath_ints = 0, stat_bytes = 0, jobs_ints = 0, anchor_ints = 0;      // the device tables; rows are positions in `order` (not pair ids)
+    bool thr = false;                     // scouts and tiles on the throughput geometry: more tile jobs than fit the device at once
+    bool smallT = false;                  // ... the tiles too on its 512-row form
+    bool longScouts = false;              // the longer margin and anchored lead (twl_knobs.inc.hip: levels of at most a round or two of tile jobs)
+    bool anchors = false;                 // mt_anchor_kernel runs in front of the scouts
+    int lead2 = 0, marg = 0, rounds = 1;
+    size_t tb_groups = 0;                 // wide: groups of 8 anti-diagonals the pair scout (MT 4) keeps of the longest pair
+};
+// `jobs` is the caller's: the upload of it is asynchronous, so it has to outlive the call.
+TilePlan plan_tile_level(const TileFacts &f, const Knobs &k, std::vector<int32_t> &jobs)
+{
+    TilePlan pl;
+    pl.slots = (2 * f.seq_len) / (f.marker - 1) + 2;
+    pl.segcap = 2 * f.marker + 16;
+    pl.sp_pitch = 2 * f.seq_len + 8;
+    pl.T.resize((size_t)f.n_run);
+    for (int t = 0; t < f.n_run; ++t) {
+        const long long RQ = (long long)f.h_len[2 * f.order[t]] + f.h_len[2 * f.order[t] + 1];
+        int n = 1;
+        while (n < pl.slots && (long long)(f.marker - 1) * n - 1 <= RQ - 2) ++n;
+        pl.T[t] = n; pl.maxT = std::max(pl.maxT, n); pl.maxRQ = std::max(pl.maxRQ, RQ);
+    }
+    // scouts for every tile boundary s >= 1 that exists, then tiles for s >= 0 (tile-major, so that the tiles of a pair spread over the launch)
+    jobs.clear();
+    for (int s = 1; s < pl.maxT; ++s) for (int t = 0; t < f.n_run; ++t) if (s < pl.T[t]) { jobs.push_back(f.order[t]); jobs.push_back(s); jobs.push_back(t); }
+    pl.nScout = (int)(jobs.size() / 3);
+    for (int s = 0; s < pl.maxT; ++s) for (int t = 0; t < f.n_run; ++t) if (s < pl.T[t]) { jobs.push_back(f.order[t]); jobs.push_back(s); jobs.push_back(t); }
+    pl.nTile = (int)(jobs.size() / 3) - pl.nScout;
+    const size_t np = (size_t)f.n_run;
+    pl.chain_ints = np * pl.slots * 2;
+    pl.rec_ints = np * pl.slots * f.rec_words;
+    pl.seg_bytes = np * pl.slots * (size_t)pl.segcap;
+    pl.spath_ints = np * (size_t)pl.sp_pitch;
+    pl.stat_bytes = 4 * sizeof(unsigned long long) + np * 8 * sizeof(int32_t);      // counters, then the per-pair frontier
+    pl.jobs_ints = jobs.size();
+    // scouts of the narrow geometries start from an anchored cell where the profiles give one (talco_nuc.hip.h, mt_anchor_kernel)
+    pl.anchors = !f.wide && k.mt_anchor && pl.nScout > 0;
+    pl.anchor_ints = pl.anchors ? np * pl.slots : 0;
+    pl.thr = !f.wide && pl.nTile > k.mt_thr_jobs;
+    // small tiles (nucleotide, throughput geometry): the tile jobs too run on 4 waves x 2 blocks, five workgroups per CU -- the earlier levels of this pass
+    // fitted the 512-row window (plan_nucleotide, small).  A tile that outgrows it leaves a failed record of a window narrower than the stitch launch's, which
+    // the stitch launch does not adopt: it computes that tile in line (run_device counts them and takes the pass off the small window when they are many).
+    pl.smallT = f.can_small && f.small_tiles;
+    // (see twl_knobs.inc.hip: longer scouts where the tile jobs are at most a round or two of the device's workgroups and a missed start a second round that lasts as long as the first)
+    pl.longScouts = !f.wide && pl.nTile <= 2048;
+    pl.lead2 = pl.longScouts ? k.mt_lead2_lat : k.mt_lead2;
+    pl.marg = pl.longScouts ? k.mt_marg_lat : k.mt_marg;
+    pl.rounds = std::max(1, std::min(k.mt_rounds, kMtMaxRounds));
+    pl.tb_groups = f.wide ? (size_t)(pl.maxRQ >> 3) + 2 : 0;
+    return pl;
+}
+// what twl_stats.kernel says of a level that started tile-parallel
+inline void tile_level_name(char *s, size_t n, const TileFacts &f, const TilePlan &pl)
+{
+    if (pl.thr && pl.smallT) snprintf(s, n, "talco_lean_kernel<%d, 4, 2, %d, 5, false, false, 2 / 1> + <%d, 16, 1, %d, 1, false, false, 3> (tile-parallel: scouts, tiles, stitch)", f.P, f.mm, f.P, f.mm);
+    else if (pl.thr) snprintf(s, n, "talco_lean_kernel<%d, %d, %d, %d, 4, false, false, 2 / 1> + <%d, 16, 1, %d, 1, false, false, 3> (tile-parallel: scouts, tiles, stitch)", f.P, f.tw, f.trpl, f.mm, f.P, f.mm);
+    else snprintf(s, n, "talco_lean_kernel<%d, 16, %d, %d, 1, false, false, 2 / 1 / 3> (tile-parallel: scouts, tiles, stitch)", f.P, f.stitch_rpl, f.mm);
+}
 
 // ---- launch policy of the protein path ----
 struct ProtFacts {

@@ -2,8 +2,6 @@
 // collect, re-run ladder (next_rung), global-memory stage, remember (PassMemory), fill twl_stats.  What the policy decides is in twl_policy.inc.hip, how a kernel family is launched in twl_launch.inc.hip.
 // Included by twl_align.hip (one translation unit: it shares that file's Device bookkeeping, error string and fill queue).
 
-Knobs current_knobs() { return Knobs{g_mt_max_pairs, g_mt_min_marker, g_mt_tail_pct, g_mt_wide, g_assume_onehot_query, g_no_spec, g_thr_small, (ProtMode)g_prot_mode, g_prot_corridor}; }
-
 // What every step of one call is given: the caller's arguments, the cost order and the kernel arguments made of them.
 struct Call {
     Device *d; hipStream_t st; const twl_params *p;

@@ -118,9 +118,13 @@ __device__ __forceinline__ void lds_max_f32(unsigned addr, float v) { asm volati
 // v_div_fixup) with the parts that depend on d alone hoisted and the scaling steps left out.  v_div_scale rescales only when
 // d or n/d is near the ends of the exponent range or |n| < 2^-103, and v_div_fixup only patches zeros, infinities and NaNs,
 // so for 1 <= d <= 2^40 and n == 0 or 2^-73 <= |n| <= 2^80 both give the same bits (a zero quotient may differ in sign, which
-// no comparison or sum downstream can see).  The kernel guards that range: profile entries and scores outside it send the
-// pair to the IEEE-division kernel (err = kErrOverflow, re-run by the next stage of the chain).  tests/test_gpu_parity.py
-// compares the two forms bit for bit on device (twl_debug_fast_div).
+// no comparison or sum downstream can see).  Three guards keep the kernels inside that range: a profile entry is zero or
+// 2^-20 <= |x| <= 2^30 (div_guard_bad below), the denominator float(refNum) * float(qryNum) lies in [1, 2^40] (talco_lean_kernel,
+// in front of the first tile), every score and gap_char is zero or within [2^-10, 2^10] (fast_div_in_range, twl_policy.inc.hip:
+// anything else plans the IEEE-division kernels from the start).  The smallest non-zero product inside them is 2^-50, whose ulp
+// is the 2^-73 above.  A pair outside the first two ends with err = kErrGuard and is re-run on the IEEE-division kernel
+// (climb_ladder, Rung::Guard); a tile that also outgrew its window reports that first.  tests/test_gpu_div_edges.py compares the
+// two forms bit for bit on device, through the DUMP instantiation of talco_lean_kernel, with operands on every one of these limits.
 __device__ __forceinline__ float fast_div(float n, float d, float r)
 {
     const float q0 = n * r;

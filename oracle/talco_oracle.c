@@ -141,6 +141,8 @@ typedef struct {
     twlo_stats *st;
     twlo_trace_fn trace;
     void *trace_user;
+    twlo_exit_fn exit_hook;
+    void *exit_user;
 } ctx_t;
 
 /* ---- Tile: TALCO-XDrop.cpp:233-689 ---------------------------------------------------------- */
@@ -379,6 +381,10 @@ static void tile_run(const ctx_t *c, int32_t *reference_idx, int32_t *query_idx,
     }
     if (*reference_idx == c->R - 1 && *query_idx == c->Q - 1) *last_tile = 1;   /* :679 */
 
+    /* the exit record (test aid): which of :615-622 / :625-632 / :633-642 the tile left through, where its walk starts, the pair after the advance */
+    if (c->exit_hook)
+        c->exit_hook(c->exit_user, tile, last_k, conv_logic ? 0 : (last_k < marker ? 1 : 2), tb_state, conv_ref_idx, conv_query_idx,
+                     *reference_idx, *query_idx);
     traceback(ftr_len, ftr_low, tb_start_addr, tb_start_ftr, (int8_t)(tb_state % 3), conv_query_idx, conv_ref_idx,
               tb.d, tb.n, aln, tile == 0);                     /* :681-682 */
     TILE_FREE();
@@ -386,12 +392,12 @@ static void tile_run(const ctx_t *c, int32_t *reference_idx, int32_t *query_idx,
 }
 
 /* ---- Align_freq: TALCO-XDrop.cpp:62-108 ----------------------------------------------------- */
-int twlo_align_pair(const twlo_params *p, const float *ref, int32_t R, const float *qry, int32_t Q,
-                    const float *gop_ref, const float *gex_ref, const float *gop_qry, const float *gex_qry,
-                    float ref_num, float qry_num, int8_t *aln, int32_t *aln_len, int16_t *err,
-                    twlo_stats *stats, twlo_trace_fn trace, void *trace_user)
+int twlo_align_pair_exits(const twlo_params *p, const float *ref, int32_t R, const float *qry, int32_t Q,
+                          const float *gop_ref, const float *gex_ref, const float *gop_qry, const float *gex_qry,
+                          float ref_num, float qry_num, int8_t *aln, int32_t *aln_len, int16_t *err,
+                          twlo_stats *stats, twlo_trace_fn trace, void *trace_user, twlo_exit_fn exit_hook, void *exit_user)
 {
-    ctx_t c = {p, ref, qry, R, Q, gop_ref, gex_ref, gop_qry, gex_qry, ref_num, qry_num, stats, trace, trace_user};
+    ctx_t c = {p, ref, qry, R, Q, gop_ref, gex_ref, gop_qry, gex_qry, ref_num, qry_num, stats, trace, trace_user, exit_hook, exit_user};
     int32_t reference_idx = 0, query_idx = 0;
     int last_tile = 0, tile = 0;
     int32_t n = 0;
@@ -414,6 +420,15 @@ int twlo_align_pair(const twlo_params *p, const float *ref, int32_t R, const flo
     free(tile_aln.d);
     *aln_len = n;
     return 0;
+}
+
+int twlo_align_pair(const twlo_params *p, const float *ref, int32_t R, const float *qry, int32_t Q,
+                    const float *gop_ref, const float *gex_ref, const float *gop_qry, const float *gex_qry,
+                    float ref_num, float qry_num, int8_t *aln, int32_t *aln_len, int16_t *err,
+                    twlo_stats *stats, twlo_trace_fn trace, void *trace_user)
+{
+    return twlo_align_pair_exits(p, ref, R, qry, Q, gop_ref, gex_ref, gop_qry, gex_qry, ref_num, qry_num, aln, aln_len, err, stats,
+                                 trace, trace_user, NULL, NULL);
 }
 
 int twlo_align_batch(const twlo_params *p, int32_t n_pairs, int32_t seq_len, const float *freq,

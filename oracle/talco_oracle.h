@@ -67,6 +67,26 @@ int twlo_align_pair(const twlo_params *p,
                     twlo_stats *stats, twlo_trace_fn trace, void *trace_user);
 
 /*
+ * Optional per-tile exit hook (test aid for the tile exit and the traceback walk of the HIP kernels).  Called once per tile that reaches
+ * the traceback, just in front of it: kind 0 the tile converged (conv_logic, :615-622), 1 the pair ended before the marker
+ * (last_k < marker, :625-632), 2 it ended at or behind the marker unconverged (CS[last_k][0], :633-642); tb_state 0..3 and
+ * conv_ref_idx / conv_query_idx are the cell and state the walk starts from; reference_idx / query_idx are the pair's after the advance
+ * (:654-655).  A tile that ends with an errorType is not reported.
+ */
+typedef void (*twlo_exit_fn)(void *user, int tile, int last_k, int kind, int tb_state, int conv_ref_idx, int conv_query_idx,
+                             int reference_idx, int query_idx);
+
+/* twlo_align_pair with the exit hook; twlo_align_pair is this with a null hook. */
+int twlo_align_pair_exits(const twlo_params *p,
+                          const float *ref, int32_t R, const float *qry, int32_t Q,
+                          const float *gop_ref, const float *gex_ref,
+                          const float *gop_qry, const float *gex_qry,
+                          float ref_num, float qry_num,
+                          int8_t *aln, int32_t *aln_len, int16_t *err,
+                          twlo_stats *stats, twlo_trace_fn trace, void *trace_user,
+                          twlo_exit_fn exit_hook, void *exit_user);
+
+/*
  * Batch form with the same flat layout as include/twl_align.h (so tests can
  * feed identical buffers to both).  Pairs are spread over `threads` OpenMP
  * threads like tbb::parallel_for at alignment-cpu.cpp:46.  stats (optional) is

@@ -24,6 +24,8 @@ class Stats(C.Structure):
 
 
 TRACE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float)
+# (user, tile, last_k, kind, tb_state, conv_ref_idx, conv_query_idx, reference_idx, query_idx): oracle/talco_oracle.h, twlo_exit_fn
+EXIT_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int)
 
 
 def lib():
@@ -36,6 +38,7 @@ def lib():
         _LIB = C.CDLL(so)
         _LIB.twlo_align_batch.restype = C.c_int
         _LIB.twlo_align_pair.restype = C.c_int
+        _LIB.twlo_align_pair_exits.restype = C.c_int
         _LIB.twlo_column_score.restype = C.c_float
     return _LIB
 
@@ -94,6 +97,25 @@ def align_pair(params: Params, ref, qry, gop_r, gex_r, gop_q, gex_q, ref_num, qr
     lib().twlo_align_pair(C.byref(params), _fp(ref), C.c_int32(R), _fp(qry), C.c_int32(Q), *[_fp(a) for a in arrs],
                           C.c_float(ref_num), C.c_float(qry_num), aln.ctypes.data_as(C.POINTER(C.c_int8)),
                           C.byref(n), C.byref(err), C.byref(st), cb, None)
+    return aln[: n.value].copy(), int(err.value), st
+
+
+def align_pair_exits(params: Params, ref, qry, gop_r, gex_r, gop_q, gex_q, ref_num, qry_num, trace=None, exits=None):
+    """align_pair through twlo_align_pair_exits: `exits(user, tile, last_k, kind, tb_state, conv_ref_idx, conv_query_idx, reference_idx,
+    query_idx)` is called once per tile that reaches its traceback (None: the null hook)."""
+    ref = np.ascontiguousarray(ref, dtype=np.float32)
+    qry = np.ascontiguousarray(qry, dtype=np.float32)
+    R, Q = ref.shape[0], qry.shape[0]
+    aln = np.zeros(R + Q, dtype=np.int8)
+    n = C.c_int32(0)
+    err = C.c_int16(0)
+    st = Stats()
+    arrs = [np.ascontiguousarray(a, dtype=np.float32) for a in (gop_r, gex_r, gop_q, gex_q)]
+    cb = TRACE_FN(trace) if trace is not None else C.cast(None, TRACE_FN)
+    ex = EXIT_FN(exits) if exits is not None else C.cast(None, EXIT_FN)
+    lib().twlo_align_pair_exits(C.byref(params), _fp(ref), C.c_int32(R), _fp(qry), C.c_int32(Q), *[_fp(a) for a in arrs],
+                                C.c_float(ref_num), C.c_float(qry_num), aln.ctypes.data_as(C.POINTER(C.c_int8)),
+                                C.byref(n), C.byref(err), C.byref(st), cb, None, ex, None)
     return aln[: n.value].copy(), int(err.value), st
 
 

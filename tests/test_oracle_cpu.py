@@ -61,6 +61,8 @@ def test_single_deletion_and_insertion_are_placed():
     assert err == 0 and (aln == 2).sum() == 5 and (aln == 1).sum() == 0
     aln2, err2, _ = run_pair(onehot(q), onehot(s))
     assert err2 == 0 and (aln2 == 1).sum() == 5 and (aln2 == 2).sum() == 0
+    go, ge = np.full(400, -50.0, dtype=np.float32), np.full(400, -5.0, dtype=np.float32)      # twlo_align_pair_exits with a null hook is twlo_align_pair
+    assert np.array_equal(O.align_pair_exits(O.make_params(M), onehot(s), onehot(q), go, ge, go[:395], ge[:395], 1.0, 1.0)[0], aln)
 
 
 @pytest.mark.parametrize("members", [(1, 1), ((2, 5), (2, 5))])

@@ -5,6 +5,8 @@
 #include "../../../include/twl_align.h"
 #include "../../../include/twl_level.h"
 
+struct twl_merge;
+
 #include <chrono>
 #include <functional>
 
@@ -75,6 +77,12 @@ FinalPaths finalPathsOfLevel(twl_store *st, const twl_params &tp, Params &param,
 struct DpTotals { double kernel = 0; uint64_t cells = 0; int retries = 0; };
 void alignWithRetry(twl_store *st, int device, const twl_params &prm, const Option &option, const std::string *retryWhat, const int16_t *knownErr, int32_t minLen,
                     int32_t *alnLen, int16_t *err, DpTotals &tot);
+// One pair of a level of merges of cached profiles (merge.cpp): the cache ids of its two sides with their Node bookkeeping (alnLen, alnNum,
+// alnWeight), the groups of the merge under each side, and what a -v retry line calls the pair.
+struct ProfilePair { int32_t refCache, qryCache, refLen, qryLen, refNum, qryNum; float refWeight, qryWeight; std::vector<int32_t> refGroups, qryGroups; std::string what; };
+struct MergeLevelTotals { double dp = 0, restore = 0, apply = 0, commit = 0; DpTotals run; int restoredOnHost = 0; };
+std::vector<int32_t> mergeProfileLevel(twl_store *st, twl_merge *mg, int device, const twl_params &tp, Params &param, const Option &option,
+                                       const std::vector<ProfilePair> &pairs, MergeLevelTotals &tot, const int16_t *knownErr = nullptr);
 inline double nowMs() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 }  // namespace gpu

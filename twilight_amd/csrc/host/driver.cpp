@@ -2,7 +2,9 @@
 // single-partition case (no -m), plus the handful of CLI flags the hot path needs (names as in twilight-main.cpp:13-84).
 #include "twl_host.hpp"
 
+#include <algorithm>
 #include <chrono>
+#include <climits>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -30,9 +32,9 @@ static int effectiveCpus()
 
 static bool flag(const char *a, const char *s, const char *l) { return (s && !strcmp(a, s)) || (l && !strcmp(a, l)); }
 
-bool parseCommandLine(int argc, char **argv, Option &o, bool allowPlacement, bool allowMerge)
+bool parseCommandLine(int argc, char **argv, Option &o, bool allowPlacement, bool allowMerge, bool allowSubtrees)
 {
-    bool typeGiven = false;
+    bool typeGiven = false, subtreesGiven = false;
     o.cpuNum = 0;
     for (int i = 1; i < argc; ++i) {
         const char *a = argv[i];
@@ -74,9 +76,22 @@ bool parseCommandLine(int argc, char **argv, Option &o, bool allowPlacement, boo
         else if (allowPlacement && flag(a, "-a", "--alignment")) o.backboneAlnFile = val();
         else if (allowPlacement && flag(a, nullptr, "--test-place-chunk")) o.testPlaceChunk = std::max(0, atoi(val()));
         else if (allowMerge && flag(a, "-f", "--files")) o.msaDir = val();
+        else if (allowSubtrees && flag(a, "-m", "--max-subtree")) {
+            const char *v = val();
+            char *end = nullptr;
+            const long n = strtol(v, &end, 10);
+            if (end == v || *end != '\0' || n < 1) { std::cerr << "ERROR: -m / --max-subtree needs a number of leaves >= 1 (got " << v << ").\n"; exit(1); }
+            o.maxSubtree = (int)std::min<long>(n, INT32_MAX);
+            subtreesGiven = true;
+        }
         else if (flag(a, nullptr, "--overwrite")) {}
         else if (flag(a, "-h", "--help")) return false;
         else { std::cerr << "ERROR: unsupported option " << a << " (this build covers the tree+sequences alignment mode only)\n"; exit(1); }
+    }
+    if (subtreesGiven) {                   // subtrees (subtrees.cpp): the tree+sequences mode only, on one GPU, rows device-resident
+        if (!o.msaDir.empty() || !o.backboneAlnFile.empty()) { std::cerr << "ERROR: -m (alignment in subtrees) cannot be combined with -a or -f.\n"; exit(1); }
+        if (o.hostStaged) { std::cerr << "ERROR: --host-staged is not available with -m (alignment in subtrees).\n"; exit(1); }
+        if (o.gpuIdx.size() > 1 || o.gpuNum > 1) { std::cerr << "ERROR: -m (alignment in subtrees) runs on one GPU: give at most one --gpu-index.\n"; exit(1); }
     }
     if (!o.msaDir.empty()) {               // merge (reference option.cpp: -f -o, nothing else to read)
         if (!o.treeFile.empty() || !o.seqFile.empty() || !o.backboneAlnFile.empty()) { std::cerr << "ERROR: -f (merging alignments) cannot be combined with -t, -i or -a.\n"; exit(1); }

@@ -2,6 +2,7 @@
 //   twilight-mi355x -t tree.nwk -i seqs.fa -o out.aln [-v] [--check] [--gpu-index 0,1,...] [scoring flags as in TWILIGHT]
 //   twilight-mi355x -a backbone.aln -i new.fa -o out.aln [...]   (built with TWL_PLACE: placement without a tree, place.cpp)
 //   twilight-mi355x -f DIR -o out.aln [...]                      (built with TWL_MERGE: the alignments of a directory merged, merge.cpp)
+//   twilight-mi355x -t tree.nwk -i seqs.fa -o out.aln -m N [...] (built with TWL_SUBTREE: the tree aligned in subtrees of at most N leaves, subtrees.cpp)
 #include "twl_host.hpp"
 
 #include "../../../include/twl_align.h"
@@ -59,12 +60,20 @@ int main(int argc, char **argv)
 #else
     const bool merging = false;
 #endif
-    if (!msa::parseCommandLine(argc, argv, option, placement, merging)) {
+#ifdef TWL_SUBTREE
+    const bool subtrees = true;
+#else
+    const bool subtrees = false;
+#endif
+    if (!msa::parseCommandLine(argc, argv, option, placement, merging, subtrees)) {
         std::cerr << "usage: twilight-mi355x -t <tree.nwk> -i <sequences.fa[.gz]> -o <out.aln> [-r 0.95] [--type n|p] [--match 18 --mismatch -8 --transition -4\n"
                      "        --gap-open -50 --gap-extend -5 --gap-ends X --xdrop 600] [-w] [--rooted] [--filter] [--check] [-v] [--gpu-index 0,1] [--host-staged]\n";
         if (placement) std::cerr << "       twilight-mi355x -a <backbone.aln[.gz]> -i <new_sequences.fa[.gz]> -o <out.aln> [scoring and filtering flags as above] [--gpu-index 0]\n";
         if (merging) std::cerr << "       twilight-mi355x -f <directory of alignments (.gz too), searched recursively> -o <out.aln> [scoring flags as above] [-r 0.95] [--type n|p] [-v] [--gpu-index 0]\n"
                                   "        (every file must hold rows of one length; the output lists the files in sorted order, rows in file order, gaps as '-')\n";
+        if (subtrees) std::cerr << "       twilight-mi355x -t <tree.nwk> -i <sequences.fa[.gz]> -o <out.aln> -m <max. leaves per subtree> [flags of the first form; one GPU, no --host-staged]\n"
+                                   "        (the tree is cut into subtrees that are aligned one after the other, their profiles are merged along the tree of subtrees;\n"
+                                   "         the output lists the subtrees in ascending index, rows in input order)\n";
         return 1;
     }
 #ifdef TWL_MERGE
@@ -81,6 +90,16 @@ int main(int argc, char **argv)
         const int W = msa::runPlacement(option);
         std::cerr << "Wrote " << option.outFile << " (length " << W << ") in " << std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - tp).count() << " s\n";
         return 0;
+    }
+#endif
+#ifdef TWL_SUBTREE
+    if (option.maxSubtree != INT32_MAX) {            // one process, one GPU (parseCommandLine refused more); -1: the tree is not split, the run is the default run
+        const auto ts = std::chrono::high_resolution_clock::now();
+        const int W = msa::runSubtrees(option);
+        if (W >= 0) {
+            std::cerr << "Wrote " << option.outFile << " (length " << W << ") in " << std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - ts).count() << " s\n";
+            return 0;
+        }
     }
 #endif
     auto t0 = std::chrono::high_resolution_clock::now();

@@ -43,7 +43,7 @@ namespace {
 
 struct MsaFile { std::string path; std::vector<std::string> names, rows; int32_t L = 0, firstId = 0; };
 
-struct MergeTotals { double count = 0, dp = 0, restore = 0, apply = 0, commit = 0, finish = 0, read = 0, write = 0; progressive::gpu::DpTotals run; int restoredOnHost = 0; };
+struct MergeTotals { double count = 0, finish = 0, read = 0, write = 0; progressive::gpu::MergeLevelTotals level; };
 
 // the files' records in order; rows: all rows at W columns back to back, or nullptr for the rows as they were read
 void writeRecords(const std::string &outFile, const std::vector<MsaFile> &files, const char *rows, int32_t W)
@@ -59,6 +59,67 @@ void writeRecords(const std::string &outFile, const std::vector<MsaFile> &files,
 }
 
 }  // namespace
+
+namespace progressive {
+namespace gpu {
+
+// One level of merges of cached profiles (alignment-cpu.cpp:50-175 with currentTask 2), shared by the merge of a directory (runMerge below:
+// a star, one pair per level) and the merge along the tree of subtrees (subtrees.cpp: levels of several pairs).  The level goes to the device
+// as ONE level of n pairs: prepare with two cached sides and no members, DP with gapCharScore 0, gappy columns back, then twl_merge_apply over
+// the groups under both sides of every pair and twl_level_commit_from_dp, which merges the two cached profiles into the reference side's.
+// A failed pair is retried until it passes (alignment-cpu.cpp:95-128).  The level's one pair is retried in place.  In a level of several
+// pairs the pairs that passed are finished first; every failed pair then becomes a level of its own, its first DP run already known (the DP
+// of a pair does not depend on the level it runs in, and the pairs of a level share no node).  Returns the final path length of every pair.
+std::vector<int32_t> mergeProfileLevel(twl_store *st, twl_merge *mg, int device, const twl_params &tp, Params &param, const Option &option,
+                                       const std::vector<ProfilePair> &pairs, MergeLevelTotals &tot, const int16_t *knownErr)
+{
+    const int32_t n = (int32_t)pairs.size();
+    std::vector<twl_side> sides;
+    std::vector<int32_t> sideLen, refOff{0}, qryOff{0}, refGroups, qryGroups;
+    int32_t maxLen = 1, stride = 1;
+    for (const ProfilePair &p : pairs) {
+        sides.push_back(twl_side{0, 0, p.refLen, p.refNum, p.refWeight, p.refCache, -1, 0});
+        sides.push_back(twl_side{0, 0, p.qryLen, p.qryNum, p.qryWeight, p.qryCache, -1, 0});
+        sideLen.push_back(p.refLen); sideLen.push_back(p.qryLen);
+        maxLen = std::max(maxLen, std::max(p.refLen, p.qryLen));
+        stride = std::max(stride, p.refLen + p.qryLen);
+        refGroups.insert(refGroups.end(), p.refGroups.begin(), p.refGroups.end());
+        qryGroups.insert(qryGroups.end(), p.qryGroups.begin(), p.qryGroups.end());
+        refOff.push_back((int32_t)refGroups.size()); qryOff.push_back((int32_t)qryGroups.size());
+    }
+    std::vector<int32_t> lenOut(2 * (size_t)n, 0), alnLen((size_t)n, 0);
+    std::vector<int16_t> err((size_t)n, 0);
+    twl_params tz = tp;
+    tz.gap_char = 0;                                       // alignment-cpu.cpp:88 (currentTask 2)
+    int rc;
+    double t0 = nowMs();
+    if ((rc = twl_level_prepare(st, &tp, option.gappyVertical, n, sides.data(), nullptr, nullptr, maxLen, lenOut.data(), nullptr)) != TWL_OK) die("twl_level_prepare", rc);
+    // alignment-cpu.cpp:95-128 with currentTask 2: retried until errorType 0
+    alignWithRetry(st, device, tz, option, n == 1 ? &pairs[0].what : nullptr, n == 1 ? knownErr : nullptr, std::min(lenOut[0], lenOut[1]), alnLen.data(), err.data(), tot.run);
+    tot.dp += nowMs() - t0;
+
+    // gappy columns back (alignment-helper.cpp:324-375) when a side lost a column; otherwise the path is final as the DP left it
+    t0 = nowMs();
+    const AlignedLevel al{n, sideLen.data(), lenOut.data(), alnLen.data(), err.data(), maxLen, stride};
+    const FinalPaths fin = finalPathsOfLevel(st, tp, param, option, al);
+    tot.restoredOnHost += fin.restoredOnHost;
+    tot.restore += nowMs() - t0;
+
+    // the maps of the groups under both sides, then the two profiles (updateAlignment / updateFrequency, alignment-cpu.cpp:169-170)
+    t0 = nowMs();
+    if ((rc = twl_merge_apply(mg, st, n, refOff.data(), refGroups.data(), qryOff.data(), qryGroups.data(), nullptr, fin.pathLen.data(), stride, fin.fromDp.data())) != TWL_OK) die("twl_merge_apply", rc);
+    tot.apply += nowMs() - t0;
+    t0 = nowMs();
+    if ((rc = twl_level_commit_from_dp(st, nullptr, fin.pathLen.data(), stride, fin.fromDp.data())) != TWL_OK) die("twl_level_commit_from_dp", rc);
+    tot.commit += nowMs() - t0;
+    std::vector<int32_t> pathLen = fin.pathLen;
+    for (int32_t i = 0; i < n; ++i)
+        if (err[i] != 0) pathLen[i] = mergeProfileLevel(st, mg, device, tp, param, option, {pairs[i]}, tot, &err[i])[0];
+    return pathLen;
+}
+
+}  // namespace gpu
+}  // namespace progressive
 
 int runMerge(Option &option)
 {
@@ -130,44 +191,15 @@ int runMerge(Option &option)
     std::vector<int32_t> rootGroups{root};
 
     const twl_params tp = baseParams(param);
-    twl_params tz = tp;
-    tz.gap_char = 0;                                       // alignment-cpu.cpp:88 (currentTask 2)
 
     // ---- one level per child, the last child first ----
     for (int32_t at = G - 1; at >= 1; --at) {
         const int32_t child = order[at];
         const int32_t qLen = files[child].L, qNum = (int32_t)files[child].names.size();
         const float qWeight = (float)qNum;
-        const int32_t maxLen = std::max(rootLen, qLen);
-        const twl_side sides[2] = {twl_side{0, 0, rootLen, rootNum, rootWeight, root, -1, 0}, twl_side{0, 0, qLen, qNum, qWeight, child, -1, 0}};
-        const int32_t sideLen[2] = {rootLen, qLen};
-        int32_t lenOut[2] = {0, 0}, alnLen = 0;
-        int16_t err = 0;
-        double t0 = nowMs();
-        if ((rc = twl_level_prepare(st, &tp, option.gappyVertical, 1, sides, nullptr, nullptr, maxLen, lenOut, nullptr)) != TWL_OK) die("twl_level_prepare", rc);
-        // alignment-cpu.cpp:95-128 with currentTask 2: retried until errorType 0
-        const std::string what = "alignment " + fs::path(files[child].path).filename().string();
-        alignWithRetry(st, device, tz, option, &what, nullptr, std::min(lenOut[0], lenOut[1]), &alnLen, &err, tot.run);
-        tot.dp += nowMs() - t0;
-
-        // gappy columns back (alignment-helper.cpp:324-375) when a side lost a column; otherwise the path is final as the DP left it
-        t0 = nowMs();
-        const int32_t stride = rootLen + qLen;
-        const progressive::gpu::AlignedLevel al{1, sideLen, lenOut, &alnLen, &err, maxLen, stride};
-        const progressive::gpu::FinalPaths fin = finalPathsOfLevel(st, tp, param, option, al);
-        const uint8_t fromDp = fin.fromDp[0];
-        const int32_t pathLen = fin.pathLen[0];
-        tot.restoredOnHost += fin.restoredOnHost;
-        tot.restore += nowMs() - t0;
-
-        // the maps of the files under both sides, then the two profiles (updateAlignment / updateFrequency, alignment-cpu.cpp:169-170)
-        t0 = nowMs();
-        const int32_t refOff[2] = {0, (int32_t)rootGroups.size()}, qryOff[2] = {0, 1};
-        if ((rc = twl_merge_apply(mg, st, 1, refOff, rootGroups.data(), qryOff, &child, nullptr, &pathLen, stride, &fromDp)) != TWL_OK) die("twl_merge_apply", rc);
-        tot.apply += nowMs() - t0;
-        t0 = nowMs();
-        if ((rc = twl_level_commit_from_dp(st, nullptr, &pathLen, stride, &fromDp)) != TWL_OK) die("twl_level_commit_from_dp", rc);
-        tot.commit += nowMs() - t0;
+        progressive::gpu::ProfilePair pr{root, child, rootLen, qLen, rootNum, qNum, rootWeight, qWeight, rootGroups, {child},
+                                         "alignment " + fs::path(files[child].path).filename().string()};
+        const int32_t pathLen = progressive::gpu::mergeProfileLevel(st, mg, device, tp, param, option, {pr}, tot.level)[0];
         // alignment-helper.cpp:474-477
         rootNum += qNum;
         rootLen = pathLen;
@@ -192,11 +224,11 @@ int runMerge(Option &option)
     t = nowMs();
     writeRecords(option.outFile, files, rows.data(), W);
     tot.write = nowMs() - t;
-    std::cerr << "Merged " << G << " alignments (" << nRows << " rows): final alignment length " << W << ", " << tot.run.retries << " retried DP run(s)\n";
+    std::cerr << "Merged " << G << " alignments (" << nRows << " rows): final alignment length " << W << ", " << tot.level.run.retries << " retried DP run(s)\n";
     if (option.printDetail)
         fprintf(stderr, "Merge phases (ms): count %.3f, prepare+DP %.3f, restore %.3f, apply %.3f, commit %.3f, finish %.3f, read-back %.3f, write %.3f; "
-                        "DP kernel %.3f ms, %llu band cells; restored on the host %d\n", tot.count, tot.dp, tot.restore, tot.apply, tot.commit, tot.finish, tot.read, tot.write,
-                tot.run.kernel, (unsigned long long)tot.run.cells, tot.restoredOnHost);
+                        "DP kernel %.3f ms, %llu band cells; restored on the host %d\n", tot.count, tot.level.dp, tot.level.restore, tot.level.apply, tot.level.commit, tot.finish, tot.read, tot.write,
+                tot.level.run.kernel, (unsigned long long)tot.level.run.cells, tot.level.restoredOnHost);
     return W;
 }
 

@@ -79,6 +79,17 @@ void updateLevels(Node *node, size_t currentLevel);
 // single-partition form of PartitionInfo::partitionTree (partitionInfo.cpp:75-85): every node joins group 0
 void assignSinglePartition(Node *root);
 
+// reference phylogeny.hpp:55-71 (partition.cpp): the tree cut into subtrees of at most maxPartitionSize leaves; grpID of every node = its subtree
+struct PartitionInfo {
+    size_t maxPartitionSize, minPartitionSize, numPartitions;
+    std::unordered_map<std::string, std::pair<Node *, size_t>> partitionsRoot;      // root of every subtree by name, with its number of leaves
+    PartitionInfo(size_t maxSize, size_t minSize, size_t num) : maxPartitionSize(maxSize), minPartitionSize(minSize), numPartitions(num) {}
+    void partitionTree(Node *root);
+    void bipartition(Node *root, Node *edge, Node *&tree1Root, Node *&tree2Root);
+};
+Tree *constructTreeFromPartitions(Node *root, PartitionInfo *P);      // phylogeny.cpp:13-39: the tree of the subtrees' roots
+void updateSubrootInfo(Node *subroot, Tree *subT, int subtreeIdx);    // tree.cpp:519-526
+
 }  // namespace phylogeny
 
 char checkOnly(char c);
@@ -309,12 +320,17 @@ int runDefaultAlignment(Option &option, alnFunction kernel, alnFunction deferred
                         const std::function<void(SequenceDB *)> &atEnd = nullptr, const std::function<void(SequenceDB *)> &beforeAlign = nullptr);
 // allowPlacement: the binary carries the placement mode (twilight-mi355x): -a/--alignment with -i/-o and no -t selects PLACE_WO_TREE
 // allowMerge: the binary carries the merge mode as well: -f/--files with -o and none of -t, -i, -a selects MERGE_MSA
-bool parseCommandLine(int argc, char **argv, Option &option, bool allowPlacement = false, bool allowMerge = false);
+// allowSubtrees: the binary carries the subtree mode too: -m/--max-subtree N with -t, -i, -o sets Option::maxSubtree
+bool parseCommandLine(int argc, char **argv, Option &option, bool allowPlacement = false, bool allowMerge = false, bool allowSubtrees = false);
 // PLACE_WO_TREE (place.cpp, libtwl_host.so): the sequences of option.seqFile placed into the alignment option.backboneAlnFile, written to
 // option.outFile.  Returns the final alignment length.
 int runPlacement(Option &option);
 // MERGE_MSA (merge.cpp, libtwl_host.so): the alignments found under option.msaDir merged into one, written to option.outFile.  Returns the
 // final alignment length.
 int runMerge(Option &option);
+// DEFAULT_ALN with -m N (subtrees.cpp, libtwl_host.so): the guide tree cut into subtrees of at most option.maxSubtree leaves, every subtree
+// aligned on its own, their profiles merged along the tree of subtrees, written to option.outFile.  Returns the final alignment length,
+// or -1 when the tree is not split (at most N leaves): nothing has been done then and the caller takes the default path.
+int runSubtrees(Option &option);
 
 }  // namespace msa

@@ -59,8 +59,11 @@ class Store:
         api._check(lib.twl_store_create(C.c_int(device), C.c_char(seq_type.encode()), C.c_int32(self.n), arr, lens, C.byref(self._h)))
         self._n_pairs = 0
         self._seq_len = 0
+        self._dependants = []        # open merges and placements on this store: they point into it, so close() ends them first
 
     def close(self):
+        for d in list(getattr(self, "_dependants", ())):
+            d.close()
         if self._h:
             _lib().twl_store_destroy(self._h)
             self._h = C.c_void_p()

@@ -2,7 +2,7 @@
 from __future__ import annotations
 
 import ctypes as C
-from typing import Sequence
+from typing import Optional, Sequence
 
 import numpy as np
 
@@ -51,6 +51,7 @@ class Merge:
         off, ids = _csr(groups)
         self.n_groups = len(groups)
         api._check(_lib().twl_merge_create(store._h, C.c_int32(self.n_groups), _p32(off), _p32(ids), C.byref(self._h)))
+        store._dependants.append(self)      # whichever of the two is closed or collected first, the merge ends before its store
         rows = store.rows_of([g[0] for g in groups]) if groups else []
         self.lengths = [len(r) for r in rows]
 
@@ -58,6 +59,8 @@ class Merge:
         if self._h:
             _lib().twl_merge_destroy(self._h)
             self._h = C.c_void_p()
+            if self in self.store._dependants:
+                self.store._dependants.remove(self)
 
     def __del__(self):
         try:
@@ -79,14 +82,22 @@ class Merge:
         api._check(_lib().twl_merge_apply(self._h, self.store._h, C.c_int32(n), _p32(roff), _p32(rg), _p32(qoff), _p32(qg),
                                           flat.ctypes.data_as(C.POINTER(C.c_int8)), _p32(plen), C.c_int32(stride), None))
 
-    def apply_level(self, ref_groups, qry_groups, path_len: Sequence[int], stride: int, from_dp: Sequence[int]) -> None:
-        """twl_merge_apply on the store's prepared and aligned level: from_dp[i] 1 = DP output, 2 = path buffer."""
+    def apply_level(self, ref_groups, qry_groups, path_len: Sequence[int], stride: int, from_dp: Sequence[int],
+                    paths: Optional[Sequence[Optional[np.ndarray]]] = None) -> None:
+        """twl_merge_apply on the store's prepared and aligned level: from_dp[i] 1 = DP output, 2 = path buffer, 0 = paths[i] (host)."""
         n = len(path_len)
         roff, rg = _csr(ref_groups)
         qoff, qg = _csr(qry_groups)
         plen = _i32(path_len)
         fd = np.ascontiguousarray(from_dp, dtype=np.uint8)
-        api._check(_lib().twl_merge_apply(self._h, self.store._h, C.c_int32(n), _p32(roff), _p32(rg), _p32(qoff), _p32(qg), None, _p32(plen), C.c_int32(stride),
+        flat = None
+        if paths is not None:
+            flat = np.zeros((max(n, 1), stride), dtype=np.int8)
+            for i, p in enumerate(paths):
+                if p is not None:
+                    flat[i, : len(p)] = p
+        api._check(_lib().twl_merge_apply(self._h, self.store._h, C.c_int32(n), _p32(roff), _p32(rg), _p32(qoff), _p32(qg),
+                                          flat.ctypes.data_as(C.POINTER(C.c_int8)) if flat is not None else None, _p32(plen), C.c_int32(stride),
                                           fd.ctypes.data_as(C.POINTER(C.c_uint8))))
 
     def map(self, g: int) -> np.ndarray:

@@ -42,11 +42,14 @@ class Placement:
         self.store, self.L = store, int(L)
         self._h = C.c_void_p()
         api._check(_lib().twl_place_create(store._h, C.c_int32(self.L), C.byref(self._h)))
+        store._dependants.append(self)      # whichever of the two is closed or collected first, the placement ends before its store
 
     def close(self):
         if self._h:
             _lib().twl_place_destroy(self._h)
             self._h = C.c_void_p()
+            if self in self.store._dependants:
+                self.store._dependants.remove(self)
 
     def __del__(self):
         try:

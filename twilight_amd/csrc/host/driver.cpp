@@ -32,7 +32,7 @@ static int effectiveCpus()
 
 static bool flag(const char *a, const char *s, const char *l) { return (s && !strcmp(a, s)) || (l && !strcmp(a, l)); }
 
-bool parseCommandLine(int argc, char **argv, Option &o, bool allowPlacement, bool allowMerge, bool allowSubtrees)
+bool parseCommandLine(int argc, char **argv, Option &o, bool allowPlacement, bool allowMerge, bool allowSubtrees, bool allowGuide)
 {
     bool typeGiven = false, subtreesGiven = false;
     o.cpuNum = 0;
@@ -84,6 +84,7 @@ bool parseCommandLine(int argc, char **argv, Option &o, bool allowPlacement, boo
             o.maxSubtree = (int)std::min<long>(n, INT32_MAX);
             subtreesGiven = true;
         }
+        else if (allowGuide && flag(a, nullptr, "--write-tree")) o.writeTreeFile = val();
         else if (flag(a, nullptr, "--overwrite")) {}
         else if (flag(a, "-h", "--help")) return false;
         else { std::cerr << "ERROR: unsupported option " << a << " (this build covers the tree+sequences alignment mode only)\n"; exit(1); }
@@ -105,7 +106,16 @@ bool parseCommandLine(int argc, char **argv, Option &o, bool allowPlacement, boo
         if (o.hostStaged) { std::cerr << "ERROR: --host-staged is not available in placement mode (-a).\n"; exit(1); }
         if (o.gpuIdx.size() > 1 || o.gpuNum > 1) { std::cerr << "ERROR: placement mode (-a) runs on one GPU: give at most one --gpu-index.\n"; exit(1); }
         o.alnMode = PLACE_WO_TREE;
+    } else if (allowGuide && o.treeFile.empty() && !o.seqFile.empty() && !o.outFile.empty()) {      // no tree: it is built from the sequences (guide.cpp), on one GPU, before anything else runs
+        if (o.gpuIdx.size() > 1 || o.gpuNum > 1) { std::cerr << "ERROR: without -t the guide tree is built on one GPU before the run starts: give at most one --gpu-index, or bring a tree with -t for a run on several.\n"; exit(1); }
+        if (o.hostStaged) { std::cerr << "ERROR: --host-staged is not available without -t (the guide tree is built on the device).\n"; exit(1); }
+        o.buildTree = true;
     } else if (o.treeFile.empty() || o.seqFile.empty() || o.outFile.empty()) return false;
+    if (!o.writeTreeFile.empty() && !o.buildTree) {
+        std::cerr << (o.treeFile.empty() ? "ERROR: --write-tree applies to a run that builds its guide tree (-i and -o without -t, -a or -f).\n"
+                                         : "ERROR: --write-tree cannot be combined with -t: a tree is written only where the run builds it.\n");
+        exit(1);
+    }
     if (o.cpuOnly) {       // the reference's GPU builds route to their CPU kernel here (hip/alignment-gpu.hip.cpp:19-21); this build has no CPU alignment path
         std::cerr << "ERROR: --cpu-only is not available: twilight-mi355x has no CPU alignment path (the CPU checker oracle/e2e_oracle is test infrastructure).\n";
         exit(1);
@@ -120,6 +130,11 @@ bool parseCommandLine(int argc, char **argv, Option &o, bool allowPlacement, boo
     return true;
 }
 
+Tree *openTree(const Option &option)
+{
+    return option.treeText.empty() ? new Tree(option.treeFile) : new Tree(Tree::FromText{}, option.treeText);
+}
+
 int runDefaultAlignment(Option &option, alnFunction kernel, alnFunction deferredKernel, bool writeOutput, const std::function<void(SequenceDB *)> &atEnd,
                         const std::function<void(SequenceDB *)> &beforeAlign)
 {
@@ -128,7 +143,7 @@ int runDefaultAlignment(Option &option, alnFunction kernel, alnFunction deferred
     SequenceDB database;
     database.updateSeqTh = option.updateSeqTh;
     Params param(option, option.type);
-    Tree *T = new Tree(option.treeFile);                                    // twilight-main.cpp:122
+    Tree *T = openTree(option);                                             // twilight-main.cpp:122
     phylogeny::assignSinglePartition(T->root);                              // :129-130 with maxSubtree = INT32_MAX
     Tree *subT = new Tree(T->root, option.reroot);                          // :145
     const double t1 = clk();

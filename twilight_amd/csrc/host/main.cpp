@@ -3,6 +3,7 @@
 //   twilight-mi355x -a backbone.aln -i new.fa -o out.aln [...]   (built with TWL_PLACE: placement without a tree, place.cpp)
 //   twilight-mi355x -f DIR -o out.aln [...]                      (built with TWL_MERGE: the alignments of a directory merged, merge.cpp)
 //   twilight-mi355x -t tree.nwk -i seqs.fa -o out.aln -m N [...] (built with TWL_SUBTREE: the tree aligned in subtrees of at most N leaves, subtrees.cpp)
+//   twilight-mi355x -i seqs.fa -o out.aln [--write-tree t.nwk]   (built with TWL_GUIDE: no tree given, the guide tree is built from the sequences, guide.cpp)
 #include "twl_host.hpp"
 
 #include "../../../include/twl_align.h"
@@ -65,7 +66,12 @@ int main(int argc, char **argv)
 #else
     const bool subtrees = false;
 #endif
-    if (!msa::parseCommandLine(argc, argv, option, placement, merging, subtrees)) {
+#ifdef TWL_GUIDE
+    const bool guide = true;
+#else
+    const bool guide = false;
+#endif
+    if (!msa::parseCommandLine(argc, argv, option, placement, merging, subtrees, guide)) {
         std::cerr << "usage: twilight-mi355x -t <tree.nwk> -i <sequences.fa[.gz]> -o <out.aln> [-r 0.95] [--type n|p] [--match 18 --mismatch -8 --transition -4\n"
                      "        --gap-open -50 --gap-extend -5 --gap-ends X --xdrop 600] [-w] [--rooted] [--filter] [--check] [-v] [--gpu-index 0,1] [--host-staged]\n";
         if (placement) std::cerr << "       twilight-mi355x -a <backbone.aln[.gz]> -i <new_sequences.fa[.gz]> -o <out.aln> [scoring and filtering flags as above] [--gpu-index 0]\n";
@@ -74,8 +80,13 @@ int main(int argc, char **argv)
         if (subtrees) std::cerr << "       twilight-mi355x -t <tree.nwk> -i <sequences.fa[.gz]> -o <out.aln> -m <max. leaves per subtree> [flags of the first form; one GPU, no --host-staged]\n"
                                    "        (the tree is cut into subtrees that are aligned one after the other, their profiles are merged along the tree of subtrees;\n"
                                    "         the output lists the subtrees in ascending index, rows in input order)\n";
+        if (guide) std::cerr << "       twilight-mi355x -i <sequences.fa[.gz]> -o <out.aln> [--write-tree <tree.nwk>] [-m N] [flags of the first form; one GPU, no --host-staged]\n"
+                                "        (no -t: the guide tree is built from the k-mers the sequences share, at most 16384 sequences, and the run goes on as with -t on that tree)\n";
         return 1;
     }
+#ifdef TWL_GUIDE
+    if (option.buildTree) option.treeText = msa::buildGuideTree(option);      // one process, one GPU (parseCommandLine refused more); from here on the run is the run of -t on this text
+#endif
 #ifdef TWL_MERGE
     if (option.alnMode == msa::MERGE_MSA) {          // one process, one GPU (parseCommandLine refused more)
         const auto tm = std::chrono::high_resolution_clock::now();
@@ -168,7 +179,7 @@ int main(int argc, char **argv)
             }
         });
     }
-    msa::progressive::gpu::beginInit(&option);
+    if (!option.buildTree) msa::progressive::gpu::beginInit(&option);      // (a run that built its tree has its device up already)
     // exit handlers run last-registered first: registered again behind whatever the GPU runtime registered while it came up, the mark is set
     // BEFORE the runtime's own teardown, which may block while other ranks sit in a collective
     if (world > 1) atexit(markFailedAtExit);

@@ -178,6 +178,12 @@ Tree::Tree(const std::string &file)        // tree.cpp:225-237 (first line of th
     parseNewick(newick);
 }
 
+Tree::Tree(FromText, const std::string &text)
+{
+    std::string newick = text.substr(0, text.find('\n'));
+    parseNewick(newick);
+}
+
 // tree.cpp:239-272: copy the nodes of node's group in stack (pre-)order into a fresh map, then reroot
 Tree::Tree(Node *node, bool doReroot)
 {

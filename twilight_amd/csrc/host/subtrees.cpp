@@ -90,7 +90,7 @@ int runSubtrees(Option &option)
     using progressive::gpu::selectedDevices;
     SubtreeTotals tot;
     Params param(option, option.type);
-    Tree *T = new Tree(option.treeFile);                                               // twilight-main.cpp:122
+    Tree *T = openTree(option);                                                        // twilight-main.cpp:122
     phylogeny::PartitionInfo P((size_t)option.maxSubtree, 0, 0);                       // :129-130
     P.partitionTree(T->root);
     if (P.partitionsRoot.size() == 1) { delete T; return -1; }                         // not split: the default run

@@ -70,6 +70,8 @@ struct Tree {
 
     Tree() = default;
     explicit Tree(const std::string &newickFileName);
+    struct FromText {};
+    Tree(FromText, const std::string &newick);      // the first line of `newick`, as the constructor above takes the first line of its file
     Tree(Node *node, bool reroot);          // copy of the nodes that share node->grpID
     ~Tree();
 };
@@ -143,6 +145,9 @@ struct Option {
     int testPlaceChunk = 0;      // --test-place-chunk n: placement aligns at most n sequences per level (default: sized to device memory)
     std::string msaDir;          // -f / --files: a directory of alignments to merge into one (alnMode MERGE_MSA)
     bool typeGiven = false;      // --type was given (a merge detects the type from its first file otherwise)
+    bool buildTree = false;      // -i and -o without -t, -a or -f: the guide tree is built from the sequences (guide.cpp)
+    std::string writeTreeFile;   // --write-tree: where the built tree is written
+    std::string treeText;        // the built tree as Newick text: read in place of treeFile (openTree)
     // scoring flags (consumed by Params)
     float match = 18, mismatch = -8, transition = -4, gapOpen = -50, gapExtend = -5, xdrop = 600;
     bool hasGapEnds = false;
@@ -321,7 +326,13 @@ int runDefaultAlignment(Option &option, alnFunction kernel, alnFunction deferred
 // allowPlacement: the binary carries the placement mode (twilight-mi355x): -a/--alignment with -i/-o and no -t selects PLACE_WO_TREE
 // allowMerge: the binary carries the merge mode as well: -f/--files with -o and none of -t, -i, -a selects MERGE_MSA
 // allowSubtrees: the binary carries the subtree mode too: -m/--max-subtree N with -t, -i, -o sets Option::maxSubtree
-bool parseCommandLine(int argc, char **argv, Option &option, bool allowPlacement = false, bool allowMerge = false, bool allowSubtrees = false);
+// allowGuide: the binary builds the guide tree itself when none is given: -i and -o without -t, -a or -f sets Option::buildTree
+bool parseCommandLine(int argc, char **argv, Option &option, bool allowPlacement = false, bool allowMerge = false, bool allowSubtrees = false, bool allowGuide = false);
+// The guide tree of a run: from option.treeText when the run built it, from the file option.treeFile otherwise; the same parser either way.
+Tree *openTree(const Option &option);
+// No -t (guide.cpp, libtwl_host.so): the sequences of option.seqFile -> shared k-mer counts of all pairs on the device -> distances -> UPGMA ->
+// Newick text, written to option.writeTreeFile when that is set.  Returns the text.
+std::string buildGuideTree(Option &option);
 // PLACE_WO_TREE (place.cpp, libtwl_host.so): the sequences of option.seqFile placed into the alignment option.backboneAlnFile, written to
 // option.outFile.  Returns the final alignment length.
 int runPlacement(Option &option);

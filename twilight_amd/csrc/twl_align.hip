@@ -7,11 +7,13 @@
 #include "../../include/twl_place.h"
 #include "../../include/twl_merge.h"
 #include "../../include/twl_subtree.h"
+#include "../../include/twl_guide.h"
 #include "level_kernels.hip.h"
 #include "restore_kernels.hip.h"
 #include "place_kernels.hip.h"
 #include "merge_kernels.hip.h"
 #include "subtree_kernels.hip.h"
+#include "guide_kernels.hip.h"
 #include "talco_kernel.hip.h"
 #include "talco_nuc.hip.h"
 #include "talco_global.hip.h"
@@ -642,3 +644,4 @@ int twl_get_pair_cells(int device, uint64_t *cells_out, int32_t n)
 #include "twl_place.inc.hip"
 #include "twl_merge.inc.hip"
 #include "twl_subtree.inc.hip"
+#include "twl_guide.inc.hip"

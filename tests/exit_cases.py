@@ -1,6 +1,8 @@
 """Directed cases for the tile exit and the traceback walk of the DP kernels (talco_nuc.hip.h, talco_kernel.hip.h, talco_global.hip.h).
 
-The three kernels each restate the reference's tile exit (TALCO-XDrop.cpp:615-682) and traceback (:134-231).  The oracle's exit hook
+The reference's tile exit (TALCO-XDrop.cpp:615-682) and the steps of its traceback (:134-231) are written once (talco_exit.hip.h: tile_exit, pair_advance,
+walk_step, the guarded append, the border fill, the segment copy; tests/test_exit_fn_cpu.py holds them on the CPU) for talco_kernel.hip.h and talco_global.hip.h,
+which keep how they fetch CS[last_k][0] and a pointer nibble and their walk loops; talco_nuc.hip.h restates the same lines.  The oracle's exit hook
 (oracle/talco_oracle.h, twlo_exit_fn) says, per tile that reaches its traceback, which exit it took: kind 0 converged, 1 the pair ended
 before the marker, 2 it ended at or behind the marker unconverged; the state the walk starts in (0 S, 1 I, 2 D, 3 the S cell one diagonal
 in front of the marker), the diagonal the tile stopped on and where the pair stands behind it.  `records` turns those and the final path

@@ -1,7 +1,8 @@
 """The tile exit and the traceback walk of every DP kernel, branch by branch, through the C ABI (-m gpu).
 
-talco_nuc.hip.h, talco_kernel.hip.h and talco_global.hip.h each restate the reference's tile exit (TALCO-XDrop.cpp:615-682) and its
-traceback (:134-231).  The pools come from tests/exit_cases.py: every exit kind and start state on tile 0 and on later tiles, pairs that
+talco_kernel.hip.h and talco_global.hip.h share the reference's tile exit (TALCO-XDrop.cpp:615-682) and the steps of its traceback
+(:134-231) through talco_exit.hip.h, each with its own fetch of CS[last_k][0] and of a pointer nibble and its own walk loop;
+talco_nuc.hip.h restates them.  Every kernel is sent every pool.  The pools come from tests/exit_cases.py: every exit kind and start state on tile 0 and on later tiles, pairs that
 end on each residue of `last_k mod 8` in front of the marker and on the diagonals around it, trailing runs short and long, border exits,
 runs that leave a 64-row x 16-group patch through its rows and through its groups, and the markers 2, 3, 7, 8, 9, 1023 and 1024.
 tests/test_exit_edge_inputs_cpu.py holds each pool to the exits it claims; here every pool of a family goes down every route of that

@@ -226,59 +226,31 @@ __global__ __launch_bounds__(1024, 1) void talco_global_kernel(GArgs ga)
             cells += tcells;
             if (tile_err) { err = tile_err; break; }
             // ---- tile exit, :615-682 ----
-            int conv_q = 0, conv_r = 0, tb_state = 0, start_k = 0;
-            bool bad = false;
             if (!conv_logic && last_k >= marker) conv_value = cS[last_k % 3][0];               // :633-635
-            if (conv_logic || last_k >= marker) {
-                conv_q = conv_value & 0xFFFF;
-                tb_state = (conv_value >> 16) & 0xFFFF;
-                if (tb_state > 3) bad = true;          // boundary sentinel / unset: the reference indexes out of range here (errorType 3, as the checker defines it)
-                else { conv_r = marker - conv_q - ((tb_state == 3) ? 1 : 0); start_k = (tb_state == 3) ? marker - 1 : marker; if (conv_r < 0) bad = true; }
-            } else { conv_q = qLen - 1; conv_r = refLen - 1; start_k = last_k; tb_state = 0; last_tile = true; }      // :625-632
-            if (bad) { err = 3; break; }
-            ref_idx += conv_r; qry_idx += conv_q;                        // :654-655
-            if (R - ref_idx < 0 || Q - qry_idx < 0) { err = 3; break; }  // :659-668
-            int tailDir = 0, tailLen = 0;
-            if (ref_idx == R - 1 && qry_idx < Q - 1) { tailDir = 1; tailLen = Q - qry_idx - 1; last_tile = true; }      // :671-674
-            if (qry_idx == Q - 1 && ref_idx < R - 1) { tailDir = 2; tailLen = R - ref_idx - 1; last_tile = true; }      // :675-678
-            if (ref_idx == R - 1 && qry_idx == Q - 1) last_tile = true;                                                 // :679
+            const TileExit ex = tile_exit(conv_logic, last_k, marker, conv_value, refLen, qLen);
+            if (ex.bad) { err = 3; break; }
+            const PairAdvance adv = pair_advance(R, Q, ex.conv_r, ex.conv_q, ref_idx, qry_idx);
+            if (adv.bad) { err = 3; break; }
+            last_tile = ex.ended_before_marker || adv.last_tile;
             // ---- Traceback, :134-231: one thread walks the pointer bytes ----
             if (tid == 0) {
-                int n = 0, kk = start_k, ii = conv_q, qi = conv_q, ri = conv_r, st = tb_state % 3;
+                int n = 0, kk = ex.start_k, ii = ex.conv_q, qi = ex.conv_q, ri = ex.conv_r, st = ex.tb_state % 3;
                 const bool first = (tile == 0);
                 while (kk >= 0) {
                     const int off = ii - s_flow[kk];
                     const int v = (off >= 0 && (size_t)off < rowcap) ? (int)tb[(size_t)kk * rowcap + (size_t)off] : 0;
-                    int dir;
-                    if (st == 0) {
-                        st = v & 3;
-                        if (st == 0) dir = 0;
-                        else if (st == 1) { dir = 1; st = (v & 4) ? 1 : 0; }
-                        else { dir = 2; st = (v & 8) ? 2 : 0; }
-                    } else if (st == 1) { dir = 1; st = (v & 4) ? 1 : 0; }
-                    else { dir = 2; st = (v & 8) ? 2 : 0; }
-                    if (dir == 0) { kk -= 2; ii -= 1; qi--; ri--; }
-                    else if (dir == 1) { kk -= 1; ii -= 1; qi--; }
-                    else { kk -= 1; ri--; }
-                    if (n < (int)sizeof(s_rev)) s_rev[n] = (int8_t)dir;
-                    ++n;
+                    rev_append(s_rev, (int)sizeof(s_rev), n, walk_step(st, v, kk, ii, qi, ri));
                     if (first && (ri < 0 || qi < 0)) break;
                     if (ii < 0) break;                 // defensive: a pointer chain left the tile (never on valid data)
                 }
-                if (first) {
-                    while (ri > -1) { if (n < (int)sizeof(s_rev)) s_rev[n] = 2; ++n; ri--; }
-                    while (qi > -1) { if (n < (int)sizeof(s_rev)) s_rev[n] = 1; ++n; qi--; }
-                }
+                if (first) border_fill(s_rev, (int)sizeof(s_rev), n, ri, qi);
                 s_misc[1] = n;
             }
             __syncthreads();
             const int n = s_misc[1];
             const int skip = (tile > 0) ? 1 : 0;                         // :98-102
-            const int cnt = n - skip;
-            if (n > (int)sizeof(s_rev) || pos + cnt + tailLen > 2 * a.seq_len) { err = 3; break; }
-            for (int t = tid; t < cnt; t += T) out[pos + t] = s_rev[n - 1 - skip - t];
-            for (int t = tid; t < tailLen; t += T) out[pos + cnt + t] = (int8_t)tailDir;
-            pos += cnt + tailLen;
+            if (n > (int)sizeof(s_rev) || pos + n - skip + adv.tailLen > 2 * a.seq_len) { err = 3; break; }
+            pos = emit_segment(out, pos, s_rev, n, skip, adv.tailDir, adv.tailLen, tid, T);
             tile += 1;
             __syncthreads();
         }

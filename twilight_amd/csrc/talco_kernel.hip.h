@@ -23,6 +23,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "talco_exit.hip.h"
 
 namespace twl {
 
@@ -668,8 +669,6 @@ __global__ __launch_bounds__(64 * W, MINW) void talco_kernel(KArgs a)
 
             // ---- tile exit, :615-682 ----
             // after the loop (L1,U1) is the band of diagonal last_k (rotated once more at its end)
-            int conv_q = 0, conv_r = 0, tb_state = 0, start_k = 0;
-            bool bad = false;
             if (!conv_logic && last_k >= marker) {                            // :633-635 needs CS[last_k][0]
                 const int Llast = L1;
 #pragma unroll
@@ -680,25 +679,11 @@ __global__ __launch_bounds__(64 * W, MINW) void talco_kernel(KArgs a)
                 __syncthreads();
                 conv_value = __builtin_amdgcn_readfirstlane(s_misc[1]);
             }
-            if (conv_logic || last_k >= marker) {
-                conv_q = conv_value & 0xFFFF;
-                tb_state = (conv_value >> 16) & 0xFFFF;
-                if (tb_state > 3) bad = true;      // boundary sentinel / unset: the reference indexes out of range here
-                else {
-                    conv_r = marker - conv_q - ((tb_state == 3) ? 1 : 0);
-                    start_k = (tb_state == 3) ? marker - 1 : marker;
-                    if (conv_r < 0) bad = true;
-                }
-            } else {                                                          // :625-632
-                conv_q = qLen - 1; conv_r = refLen - 1; start_k = last_k; tb_state = 0; last_tile = true;
-            }
-            if (bad) { err = 3; break; }
-            ref_idx += conv_r; qry_idx += conv_q;                             // :654-655
-            if (R - ref_idx < 0 || Q - qry_idx < 0) { err = 3; break; }       // :659-668
-            int tailDir = 0, tailLen = 0;
-            if (ref_idx == R - 1 && qry_idx < Q - 1) { tailDir = 1; tailLen = Q - qry_idx - 1; last_tile = true; }   // :671-674
-            if (qry_idx == Q - 1 && ref_idx < R - 1) { tailDir = 2; tailLen = R - ref_idx - 1; last_tile = true; }   // :675-678
-            if (ref_idx == R - 1 && qry_idx == Q - 1) last_tile = true;       // :679
+            const TileExit ex = tile_exit(conv_logic, last_k, marker, conv_value, refLen, qLen);
+            if (ex.bad) { err = 3; break; }
+            const PairAdvance adv = pair_advance(R, Q, ex.conv_r, ex.conv_q, ref_idx, qry_idx);
+            if (adv.bad) { err = 3; break; }
+            if (ex.ended_before_marker || adv.last_tile) last_tile = true;
 
             heartbeat(a, 6, tile);
             __syncthreads();   // all traceback-pointer stores of this tile are complete and visible
@@ -706,42 +691,23 @@ __global__ __launch_bounds__(64 * W, MINW) void talco_kernel(KArgs a)
             if (w == 0) {
                 int n = 0;
                 if (lane == 0) {   // Traceback, :134-231, addressed by (diagonal, row) instead of a ragged offset
-                    int kk = start_k, ii = conv_q, qi = conv_q, ri = conv_r, st = tb_state % 3;
+                    int kk = ex.start_k, ii = ex.conv_q, qi = ex.conv_q, ri = ex.conv_r, st = ex.tb_state % 3;
                     const bool first = (tile == 0);
                     while (kk >= 0) {
                         const uint32_t word = __hip_atomic_load(&tb[(size_t)(kk >> 3) * WINDOW + (ii % WINDOW)], __ATOMIC_RELAXED,
                                                                 __HIP_MEMORY_SCOPE_AGENT);
                         const int v = (int)((word >> (4 * (kk & 7))) & 0xFu);
-                        int dir;
-                        if (st == 0) {
-                            st = v & 3;
-                            if (st == 0) dir = 0;
-                            else if (st == 1) { dir = 1; st = (v & 4) ? 1 : 0; }
-                            else { dir = 2; st = (v & 8) ? 2 : 0; }
-                        } else if (st == 1) { dir = 1; st = (v & 4) ? 1 : 0; }
-                        else { dir = 2; st = (v & 8) ? 2 : 0; }
-                        if (dir == 0) { kk -= 2; ii -= 1; qi--; ri--; }
-                        else if (dir == 1) { kk -= 1; ii -= 1; qi--; }
-                        else { kk -= 1; ri--; }
-                        s_rev[n++] = (int8_t)dir;
+                        rev_append(s_rev, (int)sizeof(s_rev), n, walk_step(st, v, kk, ii, qi, ri));
                         if (first && (ri < 0 || qi < 0)) break;
                         if (ii < 0) break;   // defensive: a pointer chain left the tile (never on valid data)
                     }
-                    if (first) {
-                        while (ri > -1) { s_rev[n++] = 2; ri--; }
-                        while (qi > -1) { s_rev[n++] = 1; qi--; }
-                    }
+                    if (first) border_fill(s_rev, (int)sizeof(s_rev), n, ri, qi);
                 }
                 n = __builtin_amdgcn_readfirstlane(n);
                 heartbeat(a, 8, n);
                 const int skip = (tile > 0) ? 1 : 0;                          // :98-102
-                const int cnt = n - skip;
-                if (pos + cnt + tailLen > 2 * a.seq_len) { err = 3; }
-                else {
-                    for (int t = lane; t < cnt; t += 64) out[pos + t] = s_rev[n - 1 - skip - t];
-                    for (int t = lane; t < tailLen; t += 64) out[pos + cnt + t] = (int8_t)tailDir;
-                    pos += cnt + tailLen;
-                }
+                if (n > (int)sizeof(s_rev) || pos + n - skip + adv.tailLen > 2 * a.seq_len) { err = 3; }
+                else pos = emit_segment(out, pos, s_rev, n, skip, adv.tailDir, adv.tailLen, lane, 64);
                 if (lane == 0) s_misc[2] = err;
             }
             __syncthreads();

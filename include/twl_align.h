@@ -148,6 +148,29 @@ int twl_column_scores(const twl_params *p, int32_t seq_len, const float *freq, c
 int twl_dp_column_scores(const twl_params *p, int32_t seq_len, const float *freq, const float *gap_open, const float *gap_extend,
                          const int32_t *len, const int32_t *num, float *out);
 
+/* Diagnostics: the tables of the LAST tile-parallel level on `device` (talco_nuc.hip.h: anchors, scouts, chain, tile jobs, stitch), as that level left
+   them.  Read-only: the call takes the device's lock, waits for the device's stream and copies device buffers to the host; it launches no kernel and changes
+   no knob.  Rows of every table are positions in the level's launch, order[row] is the pair of a row.  A table pointer may be NULL (not copied); a first
+   call with only `dims` tells the sizes:
+     order   [n_run]                             anchor  [n_run][slots]            128 + offset of q - r, or -1 (only when dims.anchors; an error otherwise)
+     spath   [n_run][sp_pitch]                   query row of a scout's path on anti-diagonal d; -1 stepped over; < -1 unknown
+     chain   [n_run][slots][2]                   predicted start {ref, qry} of tile `slot`, as the LAST round's chain launch left it; -1 unknown
+     rec     [n_run][slots][TWL_MT_REC_WORDS]    {1 valid / 2 failed, start ref, start qry, next ref, next qry, last tile, segment bytes, tail dir, tail len,
+                                                  band cells, error code of a failed job, its window rows}
+     seg     [n_run][slots][segcap]              the tile's path segment, forward order
+     front   [n_run][8]                          {0 untouched / 1 suspended / 2 done, tile, ref, qry, path bytes, -, band cells lo, band cells hi}
+   Returns TWL_ERR_BAD_ARGUMENT when no tile-parallel level has run on the device since twl_init.  A later level (a wide re-run of the same call included)
+   overwrites the tables: they belong to the last one. */
+#define TWL_MT_REC_WORDS 12
+typedef struct twl_mt_dims {
+    int32_t n_run, slots, sp_pitch, segcap;      /* table rows; tile boundaries, words of a scout path and bytes of a segment a row has room for */
+    int32_t n_scout, n_tile, rounds;             /* scout jobs, tile jobs, rounds of chain / tiles / stitch */
+    int32_t lead2, marg, anchors;                /* anchored lead and margin of the scouts; 1 = the anchor kernel ran */
+    int32_t thr, small_tiles, marker;            /* 1 = scouts and tiles on the throughput geometry; ... tiles on its 512-row form; the call's marker */
+    int32_t reserved[3];
+} twl_mt_dims;
+int twl_mt_tables(int device, twl_mt_dims *dims, int32_t *order, int32_t *anchor, int32_t *spath, int32_t *chain, int32_t *rec, int8_t *seg, int32_t *front);
+
 /* ---- RCCL from the library's own C++ (pairs of a level sharded over the GPUs of a node, one process per GPU) ----
    The collective of a sharded run is ONE all-gather of equal byte blocks per guide-tree level, HBM to HBM over xGMI, on the library's stream of
    `device`.  librccl is loaded at run time (dlopen "librccl.so.1"; a copy already in the process, e.g. PyTorch's, is reused), so the library

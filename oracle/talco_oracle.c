@@ -422,6 +422,38 @@ int twlo_align_pair_exits(const twlo_params *p, const float *ref, int32_t R, con
     return 0;
 }
 
+/* ---- one tile from a given start: Tile() reads reference_idx / query_idx and `tile == 0`, nothing else of the tile before (:77-93) ---- */
+int twlo_tile_from(const twlo_params *p, const float *ref, int32_t R, const float *qry, int32_t Q,
+                   const float *gop_ref, const float *gex_ref, const float *gop_qry, const float *gex_qry,
+                   float ref_num, float qry_num, int32_t start_ref, int32_t start_qry, int32_t first_tile,
+                   int32_t *next_ref, int32_t *next_qry, int32_t *last_tile_out, int16_t *err,
+                   int8_t *seg, int32_t seg_cap, int32_t *seg_len, twlo_stats *stats)
+{
+    twlo_stats st;
+    memset(&st, 0, sizeof st);
+    ctx_t c = {p, ref, qry, R, Q, gop_ref, gex_ref, gop_qry, gex_qry, ref_num, qry_num, &st, NULL, NULL, NULL, NULL};
+    int32_t reference_idx = start_ref, query_idx = start_qry;
+    int last_tile = 0;
+    bytes_t tile_aln = {0, 0, 0};
+    *err = 0;
+    *seg_len = 0;
+    if (R < 1 || Q < 1 || p->marker < 2 || p->marker > 32767 || start_ref < 0 || start_qry < 0 || start_ref >= R || start_qry >= Q) return -1;
+    tile_run(&c, &reference_idx, &query_idx, &tile_aln, &last_tile, first_tile ? 0 : 1, err);
+    st.tiles = 1;
+    int32_t n = 0;
+    int rc = 0;
+    for (long i = (long)tile_aln.n - 1; i >= 0; --i) {                         /* :98-102 */
+        if (i == (long)tile_aln.n - 1 && !first_tile) continue;
+        if (n >= seg_cap) { rc = -2; break; }
+        seg[n++] = tile_aln.d[i];
+    }
+    free(tile_aln.d);
+    *seg_len = n;
+    *next_ref = reference_idx; *next_qry = query_idx; *last_tile_out = last_tile;
+    if (stats) *stats = st;
+    return rc;
+}
+
 int twlo_align_pair(const twlo_params *p, const float *ref, int32_t R, const float *qry, int32_t Q,
                     const float *gop_ref, const float *gex_ref, const float *gop_qry, const float *gex_qry,
                     float ref_num, float qry_num, int8_t *aln, int32_t *aln_len, int16_t *err,

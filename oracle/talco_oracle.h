@@ -87,6 +87,23 @@ int twlo_align_pair_exits(const twlo_params *p,
                           twlo_exit_fn exit_hook, void *exit_user);
 
 /*
+ * ONE tile from a given start cell (test aid for the tile-parallel kernels, whose records are "the tile function of the start they name"):
+ * Tile() (:233-689) from (start_ref, start_qry), as tile 0 when first_tile != 0 and as a later tile otherwise -- it reads nothing else of the
+ * tiles before it.  Out: the next start, last_tile, *err (errorType of the tile, 0 none), stats (optional) of this tile alone, and in
+ * seg[0 .. *seg_len) the tile's FORWARD path segment as Align_freq appends it (:98-102): reversed, without its first element unless
+ * first_tile, the trailing run of :671-678 at its end.  A tile that fails leaves *seg_len 0.  Returns 0, -1 for a start outside the pair,
+ * -2 when seg_cap is too small.
+ */
+int twlo_tile_from(const twlo_params *p,
+                   const float *ref, int32_t R, const float *qry, int32_t Q,
+                   const float *gop_ref, const float *gex_ref,
+                   const float *gop_qry, const float *gex_qry,
+                   float ref_num, float qry_num,
+                   int32_t start_ref, int32_t start_qry, int32_t first_tile,
+                   int32_t *next_ref, int32_t *next_qry, int32_t *last_tile, int16_t *err,
+                   int8_t *seg, int32_t seg_cap, int32_t *seg_len, twlo_stats *stats);
+
+/*
  * Batch form with the same flat layout as include/twl_align.h (so tests can
  * feed identical buffers to both).  Pairs are spread over `threads` OpenMP
  * threads like tbb::parallel_for at alignment-cpu.cpp:46.  stats (optional) is

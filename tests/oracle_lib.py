@@ -39,6 +39,7 @@ def lib():
         _LIB.twlo_align_batch.restype = C.c_int
         _LIB.twlo_align_pair.restype = C.c_int
         _LIB.twlo_align_pair_exits.restype = C.c_int
+        _LIB.twlo_tile_from.restype = C.c_int
         _LIB.twlo_column_score.restype = C.c_float
     return _LIB
 
@@ -117,6 +118,45 @@ def align_pair_exits(params: Params, ref, qry, gop_r, gex_r, gop_q, gex_q, ref_n
                                 C.c_float(ref_num), C.c_float(qry_num), aln.ctypes.data_as(C.POINTER(C.c_int8)),
                                 C.byref(n), C.byref(err), C.byref(st), cb, None, ex, None)
     return aln[: n.value].copy(), int(err.value), st
+
+
+class PairView:
+    """One pair of a LevelBatch as contiguous float32 arrays, made once and handed to tile_from many times."""
+
+    def __init__(self, batch, pair):
+        self.R, self.Q = int(batch.len[pair, 0]), int(batch.len[pair, 1])
+        self.ref = np.ascontiguousarray(batch.freq[pair, 0], dtype=np.float32)
+        self.qry = np.ascontiguousarray(batch.freq[pair, 1], dtype=np.float32)
+        self.gaps = [np.ascontiguousarray(a, dtype=np.float32) for a in (batch.gap_open[pair, 0], batch.gap_extend[pair, 0],
+                                                                             batch.gap_open[pair, 1], batch.gap_extend[pair, 1])]
+        self.num = (float(batch.num[pair, 0]), float(batch.num[pair, 1]))
+
+
+def tile_from(params: Params, pv: PairView, start, first_tile: bool):
+    """twlo_tile_from: ONE tile of pair `pv` from the cell `start` = (ref, qry).  Returns (next (ref, qry), last_tile, errorType, band cells of
+    the tile, its forward path segment as Align_freq appends it -- the trailing run included)."""
+    L = lib()
+    seg = np.zeros(pv.R + pv.Q + 2, dtype=np.int8)
+    n, nr, nq, last = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    err = C.c_int16(0)
+    st = Stats()
+    rc = L.twlo_tile_from(C.byref(params), _fp(pv.ref), C.c_int32(pv.R), _fp(pv.qry), C.c_int32(pv.Q), *[_fp(a) for a in pv.gaps],
+                          C.c_float(pv.num[0]), C.c_float(pv.num[1]), C.c_int32(int(start[0])), C.c_int32(int(start[1])), C.c_int32(1 if first_tile else 0),
+                          C.byref(nr), C.byref(nq), C.byref(last), C.byref(err), seg.ctypes.data_as(C.POINTER(C.c_int8)), C.c_int32(seg.shape[0]),
+                          C.byref(n), C.byref(st))
+    assert rc == 0, (rc, start, pv.R, pv.Q)
+    return (int(nr.value), int(nq.value)), bool(last.value), int(err.value), int(st.cells), seg[: n.value].copy()
+
+
+def pair_exits(params: Params, pv: PairView):
+    """The whole pair through twlo_align_pair_exits: (path, errorType, Stats, [(tile, kind, tb_state, next ref, next qry)] of the tiles that reached their traceback)."""
+    rows = []
+
+    def hook(_user, tile, _last_k, kind, tb_state, _cr, _cq, ridx, qidx):
+        rows.append((tile, kind, tb_state, ridx, qidx))
+
+    aln, err, st = align_pair_exits(params, pv.ref[: pv.R], pv.qry[: pv.Q], pv.gaps[0], pv.gaps[1], pv.gaps[2], pv.gaps[3], pv.num[0], pv.num[1], exits=hook)
+    return aln, err, st, rows
 
 
 def column_score(params: Params, r, q, denom):

@@ -142,3 +142,39 @@ def test_reference_layout_restatement_equals_the_checker(kind):
     assert cells == st.cells
     if kind == "err2": assert (e == 2).any()
     if kind == "err1": assert (e == 1).any()
+
+
+def _mt_case_names():
+    import mt_cases
+    return mt_cases.NAMES
+
+
+@pytest.mark.parametrize("name", _mt_case_names())
+def test_tiles_chained_from_the_corner_are_the_whole_pair(name):
+    """twlo_tile_from is one tile as a function of its start.  Chained from (0, 0) over the pairs of tests/mt_cases.py it reproduces twlo_align_pair_exits: path,
+    errorType, tiles, band cells, and the starts the exit hook reports."""
+    import mt_cases
+    c = mt_cases.case(name)
+    p = O.make_params(c.matrix, **c.pk)
+    for i in range(c.batch.n_pairs):
+        if c.batch.len[i].min() < 1:
+            continue
+        pv = O.PairView(c.batch, i)
+        aln, err, st, rows = O.pair_exits(p, pv)
+        start, first, last, segs, cells, tiles, starts, e = (0, 0), True, False, [], 0, 0, [], 0
+        while not last:
+            start, last, e, cl, seg = O.tile_from(p, pv, start, first)
+            cells += cl
+            tiles += 1
+            if e or seg.shape[0] == 0:      # (:94-97: a tile that leaves nothing ends the pair without a path)
+                segs = []
+                break
+            segs.append(seg)
+            starts.append(start)
+            first = False
+        path = np.concatenate(segs) if segs else np.zeros(0, dtype=np.int8)
+        assert e == err and tiles == st.tiles and cells == st.cells, (name, i, e, err, tiles, st.tiles, cells, st.cells)
+        assert np.array_equal(path, aln), (name, i, path.shape, aln.shape)
+        if err == 0:
+            assert starts == [(r, q) for (_t, _k, _s, r, q) in rows], (name, i)
+            assert starts[-1][0] <= pv.R - 1 and starts[-1][1] <= pv.Q - 1

@@ -20,6 +20,7 @@ from .api import (  # noqa: F401
     init,
     load_library,
     make_params,
+    mt_tables,
     set_knob,
     shutdown,
     version,

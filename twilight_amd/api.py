@@ -32,10 +32,19 @@ class TwlStats(C.Structure):
                 ("kernel", C.c_char * 160)]
 
 
+class TwlMtDims(C.Structure):
+    """twl_mt_dims -- the plan of the last tile-parallel level (include/twl_align.h, twl_mt_tables)."""
+    _fields_ = [(n, C.c_int32) for n in ("n_run", "slots", "sp_pitch", "segcap", "n_scout", "n_tile", "rounds", "lead2", "marg", "anchors", "thr",
+                                         "small_tiles", "marker")] + [("reserved", C.c_int32 * 3)]
+
+
+MT_REC_WORDS = 12      # TWL_MT_REC_WORDS
+
+
 _SYMBOLS = ["twl_init", "twl_shutdown", "twl_last_error", "twl_version", "twl_align_batch", "twl_align_batch_device",
             "twl_get_stats", "twl_get_pair_cells", "twl_column_scores", "twl_dp_column_scores", "twl_host_alloc", "twl_host_free", "twl_set_knob",
             "twl_copy_to_device", "twl_copy_from_device", "twl_copy_rows_from_device",
-            "twl_comm_unique_id", "twl_comm_init", "twl_comm_all_gather", "twl_comm_all_gather_host", "twl_comm_destroy", "twl_plan_describe"]
+            "twl_comm_unique_id", "twl_comm_init", "twl_comm_all_gather", "twl_comm_all_gather_host", "twl_comm_destroy", "twl_plan_describe", "twl_mt_tables"]
 
 
 def exported_symbols():
@@ -66,6 +75,7 @@ def load_library():
         lib.twl_dp_column_scores.restype = C.c_int
         lib.twl_shutdown.restype = None
         lib.twl_set_knob.restype = C.c_int
+        lib.twl_mt_tables.restype = C.c_int
         _lib = lib
     return _lib
 
@@ -212,3 +222,24 @@ def dp_column_scores(params: TwlParams, batch, pair: int = 0) -> np.ndarray:
     _check(load_library().twl_dp_column_scores(C.byref(params), C.c_int32(sl), _ptr(freq, C.c_float), _ptr(gop, C.c_float), _ptr(gex, C.c_float),
                                                _ptr(ln, C.c_int32), _ptr(nm, C.c_int32), _ptr(out, C.c_float)))
     return out
+
+
+def mt_tables(device=0) -> dict:
+    """twl_mt_tables: the tables the last tile-parallel level on `device` left behind -- {"dims": {...}, "order", "anchor" (None when the level ran without
+    anchors), "spath", "chain", "rec", "seg", "front"}; rows are positions in the launch, order[row] is the pair.  Read-only, launches nothing."""
+    lib = load_library()
+    dm = TwlMtDims()
+    _check(lib.twl_mt_tables(C.c_int(device), C.byref(dm), None, None, None, None, None, None, None))
+    n, s = dm.n_run, dm.slots
+    order = np.zeros(n, dtype=np.int32)
+    anchor = np.zeros((n, s), dtype=np.int32) if dm.anchors else None
+    spath = np.zeros((n, dm.sp_pitch), dtype=np.int32)
+    chain = np.zeros((n, s, 2), dtype=np.int32)
+    rec = np.zeros((n, s, MT_REC_WORDS), dtype=np.int32)
+    seg = np.zeros((n, s, dm.segcap), dtype=np.int8)
+    front = np.zeros((n, 8), dtype=np.int32)
+    _check(lib.twl_mt_tables(C.c_int(device), C.byref(dm), _ptr(order, C.c_int32), _ptr(anchor, C.c_int32) if dm.anchors else None, _ptr(spath, C.c_int32),
+                             _ptr(chain, C.c_int32), _ptr(rec, C.c_int32), _ptr(seg, C.c_int8), _ptr(front, C.c_int32)))
+    assert (dm.n_run, dm.slots) == (n, s), "another level ran between the two reads"
+    dims = {k: int(getattr(dm, k)) for k, _ in TwlMtDims._fields_ if k != "reserved"}
+    return {"dims": dims, "order": order, "anchor": anchor, "spath": spath, "chain": chain, "rec": rec, "seg": seg, "front": front}

@@ -120,7 +120,10 @@ struct Device {
     bool dump_on = false;
     std::vector<int32_t> dbg_host;
     std::vector<int32_t> mt_jobs_host;
-    Buf gc_zero;                          // [pair] flags of a call with pairs of both gap-character kinds (run_device)
+    twl_mt_dims mt_dims{};                                                       // twl_mt_tables: the plan of the last tile-parallel level (launch_mt) ...
+    std::vector<int32_t> mt_order;                                               // ... the pair of every table row ...
+    bool mt_seen = false;                                                        // ... and whether one has run since twl_init
+    Buf gc_zero;                         // [pair] flags of a call with pairs of both gap-character kinds (run_device)
     std::vector<uint8_t> gc_zero_host;
     std::vector<int16_t> last_err;                                               // error codes of the last run_device call, as read back by it
     void *probe_h = nullptr; size_t probe_cap = 0;                               // pinned: error codes of a level's sample (run_device, Throughput)
@@ -634,6 +637,16 @@ int twl_get_pair_cells(int device, uint64_t *cells_out, int32_t n)
     if (!cells_out || n < 0 || (size_t)n > d->pair_cells.size()) { g_err = "bad argument"; return TWL_ERR_BAD_ARGUMENT; }
     for (int32_t i = 0; i < n; ++i) cells_out[i] = d->pair_cells[i];
     return TWL_OK;
+}
+
+int twl_mt_tables(int device, twl_mt_dims *dims, int32_t *order, int32_t *anchor, int32_t *spath, int32_t *chain, int32_t *rec, int8_t *seg, int32_t *front)
+{
+    if (!g_init) { g_err = "twl_init not called"; return TWL_ERR_NOT_INITIALIZED; }
+    Device *d = nullptr;
+    int rc = find_dev(device, &d);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(d->mu);
+    return read_mt_tables(d, dims, order, anchor, spath, chain, rec, seg, front);
 }
 
 }  // extern "C"

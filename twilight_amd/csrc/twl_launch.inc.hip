@@ -226,6 +226,38 @@ int prepare_mt_tables(Device *d, hipStream_t st, const TilePlan &pl, const std::
     return TWL_OK;
 }
 
+// What twl_mt_tables reports of a tile-parallel level: the dims of its plan and the pair of every table row.  Host integers only.
+static_assert(TWL_MT_REC_WORDS == twl::kMtRec, "include/twl_align.h states the words of a tile's record");
+void remember_mt_plan(Device *d, const TilePlan &pl, const std::vector<int32_t> &order, int n_run, int marker)
+{
+    twl_mt_dims &m = d->mt_dims;
+    m = twl_mt_dims{};
+    m.n_run = n_run; m.slots = pl.slots; m.sp_pitch = pl.sp_pitch; m.segcap = pl.segcap; m.n_scout = pl.nScout; m.n_tile = pl.nTile; m.rounds = pl.rounds;
+    m.lead2 = pl.lead2; m.marg = pl.marg; m.anchors = pl.anchors ? 1 : 0; m.thr = pl.thr ? 1 : 0; m.small_tiles = pl.smallT ? 1 : 0; m.marker = marker;
+    d->mt_order.assign(order.begin(), order.begin() + n_run);
+    d->mt_seen = true;
+}
+// twl_mt_tables: plain copies of the buffers the last tile-parallel level left behind, after the device's stream has drained.  No launch.
+int read_mt_tables(Device *d, twl_mt_dims *dims, int32_t *order, int32_t *anchor, int32_t *spath, int32_t *chain, int32_t *rec, int8_t *seg, int32_t *front)
+{
+    if (!d->mt_seen) { g_err = "no tile-parallel level has run on this device since twl_init"; return TWL_ERR_BAD_ARGUMENT; }
+    const twl_mt_dims &m = d->mt_dims;
+    if (anchor && !m.anchors) { g_err = "the last tile-parallel level ran without anchors: there is no anchor table"; return TWL_ERR_BAD_ARGUMENT; }
+    HIP_TRY(hipSetDevice(d->id));
+    HIP_TRY(hipStreamSynchronize(d->stream));
+    const size_t np = (size_t)m.n_run, ns = np * (size_t)m.slots;
+    if (dims) *dims = m;
+    if (order) std::copy(d->mt_order.begin(), d->mt_order.end(), order);
+    if (np == 0) return TWL_OK;
+    if (anchor) HIP_TRY(hipMemcpy(anchor, d->mt_anchor.p, ns * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (spath) HIP_TRY(hipMemcpy(spath, d->mt_spath.p, np * (size_t)m.sp_pitch * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (chain) HIP_TRY(hipMemcpy(chain, d->mt_chain.p, ns * 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (rec) HIP_TRY(hipMemcpy(rec, d->mt_rec.p, ns * twl::kMtRec * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (seg) HIP_TRY(hipMemcpy(seg, d->mt_seg.p, ns * (size_t)m.segcap, hipMemcpyDeviceToHost));
+    if (front) HIP_TRY(hipMemcpy(front, (const unsigned long long *)d->mt_stat.p + 4, np * 8 * sizeof(int32_t), hipMemcpyDeviceToHost));      // (behind the four counters: launch_mt, mt_front)
+    return TWL_OK;
+}
+
 // Tile-parallel alignment of a level with few pairs (talco_nuc.hip.h, MT kernels): scouts, then rounds of chain -> tiles -> stitch, on `st`.
 // `order` = the pairs that run, h_len their lengths on the host.  Scouts and tiles run on the 16-wave geometry (one workgroup per CU, the
 // shortest diagonal step) while they fit the device at once (one workgroup per CU), on the throughput geometry (8 waves x 2 blocks, two per CU) beyond.
@@ -252,6 +284,7 @@ int launch_mt(Device *d, hipStream_t st, const twl::KArgs &base, const int32_t *
     const TilePlan pl = plan_tile_level(f, k, d->mt_jobs_host);       // (the jobs are kept with the device: their upload is asynchronous)
     int rc;
     if ((rc = prepare_mt_tables(d, st, pl, d->mt_jobs_host))) return rc;
+    remember_mt_plan(d, pl, order, n_run, base.marker);
     twl::NArgs a = lean_args(d, base);
     a.items = d_items;
     a.mt_chain = (int32_t *)d->mt_chain.p; a.mt_rec = (int32_t *)d->mt_rec.p; a.mt_seg = (int8_t *)d->mt_seg.p; a.mt_spath = (int32_t *)d->mt_spath.p;

@@ -45,6 +45,37 @@ int twl_guide_shared(int device, char type, int32_t n, const char *const *seqs, 
 /* Milliseconds of the last twl_guide_shared of this device: upload + count kernel, all-pairs kernel, download. */
 int twl_guide_timing(int device, double *count_ms, double *pairs_ms, double *download_ms);
 
+/*
+ * The two-stage tree (`--tree-seeds S`): a set keeps the counts c_i and the sums w_i of up to TWL_GUIDE_SET_MAX_SEQS
+ * sequences on the device, and the calls below work on it; no matrix over the whole set is ever formed.  Sequences are named by their
+ * index in the call that made the set.  Refused before any device work, each with a text of its own: what twl_guide_shared refuses (with the
+ * larger cap), a NULL set or pointer, n_seeds outside 1 .. TWL_GUIDE_MAX_SEQS, a seed or sequence id outside the set, the same seed twice,
+ * no group, an empty group, a group of more than TWL_GUIDE_MAX_SEQS sequences, group offsets that do not start at 0 or that decrease, and
+ * groups whose matrices hold more than 2^28 entries together (the 1 GiB of twl_guide_shared's largest matrix).
+ */
+#define TWL_GUIDE_SET_MAX_SEQS 1048576
+
+typedef struct twl_guide_set twl_guide_set;
+
+/* Uploads the sequences and counts their k-mers.  Panels that do not fit the device's free memory: TWL_ERR_HIP, the text says "out of device memory". */
+int twl_guide_set_create(int device, char type, int32_t n, const char *const *seqs, const int32_t *lens, twl_guide_set **set);
+int twl_guide_set_destroy(twl_guide_set *set);
+
+/* w_out[i] = w_i, i < n. */
+int twl_guide_set_weights(twl_guide_set *set, uint32_t *w_out);
+
+/* seed_out[i] = the index t into seed_ids of the seed sequence i goes to, shared_out[i] = S(i, seed_ids[t]) (shared_out may be NULL).
+   A sequence that is a seed goes to itself; every other one to the t with the largest S(i, seed_ids[t]) / min(w_i, w_seed), taken as 0 / 1
+   where that minimum is 0, compared exactly (by cross-multiplying in 64-bit integers), the smaller t among equals. */
+int twl_guide_set_assign(twl_guide_set *set, int32_t n_seeds, const int32_t *seed_ids, int32_t *seed_out, uint32_t *shared_out);
+
+/* The S-matrix of every group in one launch: the rows of group g are ids[group_off[g] .. group_off[g + 1]), m_g of them, and its block
+   (m_g x m_g, row-major, symmetric, w on the diagonal) starts at out[sum of m_h^2 over h < g].  group_off has n_groups + 1 entries. */
+int twl_guide_set_shared_groups(twl_guide_set *set, int32_t n_groups, const int32_t *group_off, const int32_t *ids, uint32_t *out);
+
+/* Milliseconds spent on this set since it was made: upload + count kernel, assign kernels, group kernels, and all downloads. */
+int twl_guide_set_timing(twl_guide_set *set, double *count_ms, double *assign_ms, double *groups_ms, double *download_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -85,6 +85,13 @@ bool parseCommandLine(int argc, char **argv, Option &o, bool allowPlacement, boo
             subtreesGiven = true;
         }
         else if (allowGuide && flag(a, nullptr, "--write-tree")) o.writeTreeFile = val();
+        else if (allowGuide && flag(a, nullptr, "--tree-seeds")) {
+            const char *v = val();
+            char *end = nullptr;
+            const long n = strtol(v, &end, 10);
+            if (end == v || *end != '\0' || n < 2 || n > 16384) { std::cerr << "ERROR: --tree-seeds needs a number of seeds from 2 to 16384 (got " << v << ").\n"; exit(1); }
+            o.treeSeeds = (int)n;
+        }
         else if (flag(a, nullptr, "--overwrite")) {}
         else if (flag(a, "-h", "--help")) return false;
         else { std::cerr << "ERROR: unsupported option " << a << " (this build covers the tree+sequences alignment mode only)\n"; exit(1); }
@@ -114,6 +121,10 @@ bool parseCommandLine(int argc, char **argv, Option &o, bool allowPlacement, boo
     if (!o.writeTreeFile.empty() && !o.buildTree) {
         std::cerr << (o.treeFile.empty() ? "ERROR: --write-tree applies to a run that builds its guide tree (-i and -o without -t, -a or -f).\n"
                                          : "ERROR: --write-tree cannot be combined with -t: a tree is written only where the run builds it.\n");
+        exit(1);
+    }
+    if (o.treeSeeds > 0 && !o.buildTree) {
+        std::cerr << "ERROR: --tree-seeds applies to a run that builds its guide tree (-i and -o without -t, -a or -f).\n";
         exit(1);
     }
     if (o.cpuOnly) {       // the reference's GPU builds route to their CPU kernel here (hip/alignment-gpu.hip.cpp:19-21); this build has no CPU alignment path

@@ -3,7 +3,7 @@
 //   twilight-mi355x -a backbone.aln -i new.fa -o out.aln [...]   (built with TWL_PLACE: placement without a tree, place.cpp)
 //   twilight-mi355x -f DIR -o out.aln [...]                      (built with TWL_MERGE: the alignments of a directory merged, merge.cpp)
 //   twilight-mi355x -t tree.nwk -i seqs.fa -o out.aln -m N [...] (built with TWL_SUBTREE: the tree aligned in subtrees of at most N leaves, subtrees.cpp)
-//   twilight-mi355x -i seqs.fa -o out.aln [--write-tree t.nwk]   (built with TWL_GUIDE: no tree given, the guide tree is built from the sequences, guide.cpp)
+//   twilight-mi355x -i seqs.fa -o out.aln [--write-tree t.nwk] [--tree-seeds S]   (built with TWL_GUIDE: no tree given, the guide tree is built from the sequences, guide.cpp)
 #include "twl_host.hpp"
 
 #include "../../../include/twl_align.h"
@@ -80,8 +80,9 @@ int main(int argc, char **argv)
         if (subtrees) std::cerr << "       twilight-mi355x -t <tree.nwk> -i <sequences.fa[.gz]> -o <out.aln> -m <max. leaves per subtree> [flags of the first form; one GPU, no --host-staged]\n"
                                    "        (the tree is cut into subtrees that are aligned one after the other, their profiles are merged along the tree of subtrees;\n"
                                    "         the output lists the subtrees in ascending index, rows in input order)\n";
-        if (guide) std::cerr << "       twilight-mi355x -i <sequences.fa[.gz]> -o <out.aln> [--write-tree <tree.nwk>] [-m N] [flags of the first form; one GPU, no --host-staged]\n"
-                                "        (no -t: the guide tree is built from the k-mers the sequences share, at most 16384 sequences, and the run goes on as with -t on that tree)\n";
+        if (guide) std::cerr << "       twilight-mi355x -i <sequences.fa[.gz]> -o <out.aln> [--write-tree <tree.nwk>] [--tree-seeds S] [-m N] [flags of the first form; one GPU, no --host-staged]\n"
+                                "        (no -t: the guide tree is built from the k-mers the sequences share, at most 16384 sequences, and the run goes on as with -t on that tree;\n"
+                                "         --tree-seeds S builds it in two stages around S seed sequences, for more sequences than that: S near twice the square root of their number)\n";
         return 1;
     }
 #ifdef TWL_GUIDE

@@ -147,6 +147,7 @@ struct Option {
     bool typeGiven = false;      // --type was given (a merge detects the type from its first file otherwise)
     bool buildTree = false;      // -i and -o without -t, -a or -f: the guide tree is built from the sequences (guide.cpp)
     std::string writeTreeFile;   // --write-tree: where the built tree is written
+    int treeSeeds = 0;           // --tree-seeds S: the tree is built in two stages around S seed sequences (guide.cpp); 0: in one
     std::string treeText;        // the built tree as Newick text: read in place of treeFile (openTree)
     // scoring flags (consumed by Params)
     float match = 18, mismatch = -8, transition = -4, gapOpen = -50, gapExtend = -5, xdrop = 600;
@@ -332,6 +333,7 @@ bool parseCommandLine(int argc, char **argv, Option &option, bool allowPlacement
 Tree *openTree(const Option &option);
 // No -t (guide.cpp, libtwl_host.so): the sequences of option.seqFile -> shared k-mer counts of all pairs on the device -> distances -> UPGMA ->
 // Newick text, written to option.writeTreeFile when that is set.  Returns the text.
+// With option.treeSeeds > 0 the tree is built in two stages (section 4g): seeds, clusters around them, a tree per cluster grafted onto the seeds' tree.
 std::string buildGuideTree(Option &option);
 // PLACE_WO_TREE (place.cpp, libtwl_host.so): the sequences of option.seqFile placed into the alignment option.backboneAlnFile, written to
 // option.outFile.  Returns the final alignment length.

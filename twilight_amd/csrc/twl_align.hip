@@ -658,3 +658,4 @@ int twl_mt_tables(int device, twl_mt_dims *dims, int32_t *order, int32_t *anchor
 #include "twl_merge.inc.hip"
 #include "twl_subtree.inc.hip"
 #include "twl_guide.inc.hip"
+#include "twl_guide_set.inc.hip"

@@ -34,7 +34,7 @@ static bool flag(const char *a, const char *s, const char *l) { return (s && !st
 
 bool parseCommandLine(int argc, char **argv, Option &o, bool allowPlacement, bool allowMerge, bool allowSubtrees, bool allowGuide)
 {
-    bool typeGiven = false, subtreesGiven = false;
+    bool typeGiven = false, subtreesGiven = false, maskGiven = false;
     o.cpuNum = 0;
     for (int i = 1; i < argc; ++i) {
         const char *a = argv[i];
@@ -92,9 +92,31 @@ bool parseCommandLine(int argc, char **argv, Option &o, bool allowPlacement, boo
             if (end == v || *end != '\0' || n < 2 || n > 16384) { std::cerr << "ERROR: --tree-seeds needs a number of seeds from 2 to 16384 (got " << v << ").\n"; exit(1); }
             o.treeSeeds = (int)n;
         }
+        else if (allowGuide && flag(a, nullptr, "--iterations")) {
+            const char *v = val();
+            char *end = nullptr;
+            const long n = strtol(v, &end, 10);
+            if (end == v || *end != '\0' || n < 1 || n > 5) { std::cerr << "ERROR: --iterations needs a number of runs from 1 to 5 (got " << v << ").\n"; exit(1); }
+            o.iterations = (int)n;
+        }
+        else if (allowGuide && flag(a, nullptr, "--mask-gappy")) {
+            const char *v = val();
+            char *end = nullptr;
+            const double t = strtod(v, &end);
+            if (end == v || *end != '\0' || !(t > 0.0 && t <= 1.0)) { std::cerr << "ERROR: --mask-gappy needs a value in (0, 1] (got " << v << ").\n"; exit(1); }
+            o.maskGappy = t;
+            maskGiven = true;
+        }
         else if (flag(a, nullptr, "--overwrite")) {}
         else if (flag(a, "-h", "--help")) return false;
         else { std::cerr << "ERROR: unsupported option " << a << " (this build covers the tree+sequences alignment mode only)\n"; exit(1); }
+    }
+    if (maskGiven && o.iterations < 2) { std::cerr << "ERROR: --mask-gappy applies to the trees that --iterations 2 or more rebuilds from an alignment.\n"; exit(1); }
+    if (o.iterations > 1) {                // iterations (retree.cpp): the tree+sequences run or the run that builds its tree, repeated on one GPU, rows device-resident
+        if (!o.backboneAlnFile.empty() || !o.msaDir.empty() || subtreesGiven) { std::cerr << "ERROR: --iterations cannot be combined with -a, -f or -m.\n"; exit(1); }
+        if (!o.noFilter) { std::cerr << "ERROR: --iterations cannot be combined with --filter: the rebuilt tree would lack the excluded sequences.\n"; exit(1); }
+        if (o.hostStaged) { std::cerr << "ERROR: --host-staged is not available with --iterations.\n"; exit(1); }
+        if (o.gpuIdx.size() > 1 || o.gpuNum > 1) { std::cerr << "ERROR: --iterations runs on one GPU: give at most one --gpu-index.\n"; exit(1); }
     }
     if (subtreesGiven) {                   // subtrees (subtrees.cpp): the tree+sequences mode only, on one GPU, rows device-resident
         if (!o.msaDir.empty() || !o.backboneAlnFile.empty()) { std::cerr << "ERROR: -m (alignment in subtrees) cannot be combined with -a or -f.\n"; exit(1); }
@@ -168,6 +190,7 @@ int runDefaultAlignment(Option &option, alnFunction kernel, alnFunction deferred
     if (writeOutput) io::writeFinalMSA(&database, &option, alnLen);        // :165
     if (option.printDetail)
         std::cerr << "Driver phases (s): tree " << t1 - t0 << ", read " << t2 - t1 << ", align " << t3 - t2 << ", write " << clk() - t3 << '\n';
+    database.finalAlnLen = alnLen;
     if (atEnd) atEnd(&database);
     delete subT;
     delete T;

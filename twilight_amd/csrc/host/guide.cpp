@@ -22,7 +22,7 @@ namespace msa {
 using progressive::gpu::die;
 using progressive::gpu::nowMs;
 
-static void refuseName(const std::string &name)
+void refuseName(const std::string &name)
 {
     if (name.empty()) { std::cerr << "ERROR: a sequence without a name cannot be a leaf of the guide tree; name every record, or bring a tree with -t.\n"; exit(1); }
     for (char c : name)

@@ -45,6 +45,21 @@ inline Triangle distances(int n, const uint32_t *shared)
     return d;
 }
 
+// d(i, j) = 1 - match(i, j) / both(i, j) in double, 1 where both is 0; match, both: N x N
+inline Triangle distancesFromCounts(int n, const uint32_t *match, const uint32_t *both)
+{
+    Triangle d(n);
+#ifdef _OPENMP
+#pragma omp parallel for schedule(dynamic, 16) if (n >= 2048)
+#endif
+    for (int a = 0; a < n; ++a)
+        for (int b = a + 1; b < n; ++b) {
+            const uint32_t m = match[(size_t)a * n + b], c = both[(size_t)a * n + b];
+            d.at(a, b) = c == 0 ? 1.0 : 1.0 - (double)m / (double)c;
+        }
+    return d;
+}
+
 struct Merge { int left, right; double height; };      // nodes: leaves 0 .. N-1, the cluster of step s is N + s
 
 // The N-1 merges of the definition above, in order.  d is consumed.

@@ -149,6 +149,8 @@ struct Option {
     std::string writeTreeFile;   // --write-tree: where the built tree is written
     int treeSeeds = 0;           // --tree-seeds S: the tree is built in two stages around S seed sequences (guide.cpp); 0: in one
     std::string treeText;        // the built tree as Newick text: read in place of treeFile (openTree)
+    int iterations = 1;          // --iterations K: the run is repeated K times, runs 2 .. K on a tree computed from the alignment of the run before (retree.cpp)
+    double maskGappy = 0.95;     // --mask-gappy T: a column with more than floor(T * N) gaps does not enter that tree's distances
     // scoring flags (consumed by Params)
     float match = 18, mismatch = -8, transition = -4, gapOpen = -50, gapExtend = -5, xdrop = 600;
     bool hasGapEnds = false;
@@ -189,6 +191,7 @@ struct SequenceDB {
         ~SequenceInfo();
     };
     int currentTask = 0;
+    int finalAlnLen = 0;                           // the alignment length of the finished run (runDefaultAlignment sets it before its atEnd hook)
     int updateSeqTh = 1000;                        // Option::updateSeqTh of the run (updateAlignment has no Option)
     std::vector<SequenceInfo *> sequences;
     std::vector<Node *> fallback_nodes;
@@ -328,6 +331,7 @@ int runDefaultAlignment(Option &option, alnFunction kernel, alnFunction deferred
 // allowMerge: the binary carries the merge mode as well: -f/--files with -o and none of -t, -i, -a selects MERGE_MSA
 // allowSubtrees: the binary carries the subtree mode too: -m/--max-subtree N with -t, -i, -o sets Option::maxSubtree
 // allowGuide: the binary builds the guide tree itself when none is given: -i and -o without -t, -a or -f sets Option::buildTree
+//             ... and knows --iterations K and --mask-gappy T (retree.cpp); without it both are unsupported options
 bool parseCommandLine(int argc, char **argv, Option &option, bool allowPlacement = false, bool allowMerge = false, bool allowSubtrees = false, bool allowGuide = false);
 // The guide tree of a run: from option.treeText when the run built it, from the file option.treeFile otherwise; the same parser either way.
 Tree *openTree(const Option &option);
@@ -335,6 +339,12 @@ Tree *openTree(const Option &option);
 // Newick text, written to option.writeTreeFile when that is set.  Returns the text.
 // With option.treeSeeds > 0 the tree is built in two stages (section 4g): seeds, clusters around them, a tree per cluster grafted onto the seeds' tree.
 std::string buildGuideTree(Option &option);
+// What buildGuideTree refuses about a sequence name (it could not be a leaf of a written tree): ends the run with a message.
+void refuseName(const std::string &name);
+// --iterations K, K >= 2 (retree.cpp, libtwl_host.so): the default alignment K times; after every run but the last the guide tree is computed anew
+// from the finished rows (pair counts on the device, include/twl_retree.h; distances, UPGMA and text on the host).  The first tree is the
+// user's (-t) or the k-mer tree.  Only the last alignment is written; option.writeTreeFile receives the tree it was built on.  Returns its length.
+int runIterations(Option &option);
 // PLACE_WO_TREE (place.cpp, libtwl_host.so): the sequences of option.seqFile placed into the alignment option.backboneAlnFile, written to
 // option.outFile.  Returns the final alignment length.
 int runPlacement(Option &option);

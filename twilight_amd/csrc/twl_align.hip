@@ -8,12 +8,14 @@
 #include "../../include/twl_merge.h"
 #include "../../include/twl_subtree.h"
 #include "../../include/twl_guide.h"
+#include "../../include/twl_retree.h"
 #include "level_kernels.hip.h"
 #include "restore_kernels.hip.h"
 #include "place_kernels.hip.h"
 #include "merge_kernels.hip.h"
 #include "subtree_kernels.hip.h"
 #include "guide_kernels.hip.h"
+#include "retree_kernels.hip.h"
 #include "talco_kernel.hip.h"
 #include "talco_nuc.hip.h"
 #include "talco_global.hip.h"
@@ -659,3 +661,4 @@ int twl_mt_tables(int device, twl_mt_dims *dims, int32_t *order, int32_t *anchor
 #include "twl_subtree.inc.hip"
 #include "twl_guide.inc.hip"
 #include "twl_guide_set.inc.hip"
+#include "twl_retree.inc.hip"

@@ -231,10 +231,13 @@ int twl_comm_destroy(int device);
                              only: the results are the same either way (tests hold the two to each other).  TWL_KNOB_MT_LEAD2: 128 on levels of at most 2048 tile jobs;
                              a value >= 0 sets both kinds of level to it (at least 16), a negative value restores both defaults, 96 / 128
      TWL_KNOB_PROT_CORRIDOR  rows (default 448): protein levels of few pairs precompute their column scores (matrix mode 4) only within this many rows of the straight line
-                             between the corners of a pair's matrix; a pair whose band leaves that corridor is re-run by the kernel that scores in line.  0: the whole matrix */
+                             between the corners of a pair's matrix; a pair whose band leaves that corridor is re-run by the kernel that scores in line.  0: the whole matrix
+     TWL_KNOB_TAIL_OVERLAP   1 (default): the remainder of a throughput level (TWL_KNOB_MT_TAIL_PCT) is launched on a stream of its own, with its own traceback scratch and work
+                             counters, so that its scouts and tile jobs fill the workgroup slots the bulk launch frees as its pairs end; 0: behind the bulk launch on the
+                             call's stream (the order before).  The same results either way (tests hold both to the oracle) */
 enum twl_knob { TWL_KNOB_MT_PERTURB = 1, TWL_KNOB_MT_MAX_PAIRS = 2, TWL_KNOB_MT_MIN_MARKER = 3, TWL_KNOB_MT_LEAD = 4, TWL_KNOB_MT_MARGIN = 5,
                 TWL_KNOB_MT_ROUNDS = 6, TWL_KNOB_MT_THR_JOBS = 7, TWL_KNOB_FAIL_ROW_ALLOCS = 8,
-                TWL_KNOB_PROT_MODE = 9, TWL_KNOB_ASSUME_ONEHOT_QUERY = 10, TWL_KNOB_MT_TAIL_PCT = 11, TWL_KNOB_MT_WIDE = 12, TWL_KNOB_NO_SPEC = 13, TWL_KNOB_SCOUT_XDROP_PCT = 14, TWL_KNOB_THR_SMALL = 15, TWL_KNOB_FORCE_GLOBAL = 16, TWL_KNOB_LEAF_STEP = 17, TWL_KNOB_POISON_TB = 18, TWL_KNOB_MT_ANCHOR = 19, TWL_KNOB_MT_LEAD2 = 20, TWL_KNOB_PROT_CORRIDOR = 21 };
+                TWL_KNOB_PROT_MODE = 9, TWL_KNOB_ASSUME_ONEHOT_QUERY = 10, TWL_KNOB_MT_TAIL_PCT = 11, TWL_KNOB_MT_WIDE = 12, TWL_KNOB_NO_SPEC = 13, TWL_KNOB_SCOUT_XDROP_PCT = 14, TWL_KNOB_THR_SMALL = 15, TWL_KNOB_FORCE_GLOBAL = 16, TWL_KNOB_LEAF_STEP = 17, TWL_KNOB_POISON_TB = 18, TWL_KNOB_MT_ANCHOR = 19, TWL_KNOB_MT_LEAD2 = 20, TWL_KNOB_PROT_CORRIDOR = 21, TWL_KNOB_TAIL_OVERLAP = 22 };
 int twl_set_knob(int key, int value);
 /* The launch plan of a nucleotide call in words ("throughput; mode 2; window 768; bulk 1024 tail 277"), made by the very function the launch path
    uses, without touching a device: len[n_pairs][2] as twl_align_batch, num_cu / qry_onehot / wide_streak the facts the device would supply. */

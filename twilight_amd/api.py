@@ -159,6 +159,7 @@ KNOB_POISON_TB = 18
 KNOB_MT_ANCHOR = 19
 KNOB_PROT_CORRIDOR = 21
 KNOB_MT_LEAD2 = 20
+KNOB_TAIL_OVERLAP = 22
 PROT_MODES = {"auto": 0, "dense": 1, "sparse": 2, "presim": 3, "r1": 4, "lean_sparse": 5, "lean_presim": 6}
 
 

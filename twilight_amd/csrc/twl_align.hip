@@ -111,6 +111,11 @@ struct Device {
     hipStream_t stream = nullptr;
     hipStream_t stream2 = nullptr;                                               // row rewrites of small levels (twl_level_commit), beside the next level's work on `stream`
     hipEvent_t ev2[2] = {};                                                      // ... timed
+    hipStream_t tail_stream = nullptr;                                           // the tile-parallel remainder of a throughput level, beside its bulk launch on the call's stream (first_throughput); lowest priority
+    hipEvent_t tail_ev[2] = {};                                                  // ... fork (in front of the bulk kernel) and join (behind the remainder's last launch)
+    Buf tb_tail;                                                                 // ... its traceback scratch: d->tb is the running bulk's
+    bool tail_side = false;                                                      // launch_mt is running for that remainder: tb_tail and the second block of work counters (kTailCounterBase)
+    bool fork_next = false;                                                      // launch_lean records tail_ev[0] between its fills and its kernel
     hipEvent_t ev[8] = {};                                                       // [6], [7]: the write-back of a level (twl_level_commit, read later by twl_level_timing)
     int num_cu = 0;
     Buf cols, tb, cells, queue, items, errs, dbg;
@@ -227,7 +232,9 @@ int twl_init(const int *device_ids, int n_devices)
             for (auto &e : d->ev) if (e) (void)hipEventDestroy(e);
             if (d->stream) (void)hipStreamDestroy(d->stream);
             if (d->stream2) (void)hipStreamDestroy(d->stream2);
+            if (d->tail_stream) (void)hipStreamDestroy(d->tail_stream);
             for (auto &e : d->ev2) if (e) (void)hipEventDestroy(e);
+            for (auto &e : d->tail_ev) if (e) (void)hipEventDestroy(e);
             delete d;
         }
         return rc;
@@ -240,8 +247,9 @@ int twl_init(const int *device_ids, int n_devices)
         hipDeviceProp_t prop;
         hipError_t e = hipSetDevice(id);
         if (e == hipSuccess) e = hipGetDeviceProperties(&prop, id);
-        if (e == hipSuccess) { d->num_cu = prop.multiProcessorCount; e = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking); if (e == hipSuccess) { int least = 0, greatest = 0; (void)hipDeviceGetStreamPriorityRange(&least, &greatest); e = hipStreamCreateWithPriority(&d->stream2, hipStreamNonBlocking, least); } }      // (the row rewrites there give way to the DP kernels of the first stream)
+        if (e == hipSuccess) { d->num_cu = prop.multiProcessorCount; e = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking); if (e == hipSuccess) { int least = 0, greatest = 0; (void)hipDeviceGetStreamPriorityRange(&least, &greatest); e = hipStreamCreateWithPriority(&d->stream2, hipStreamNonBlocking, least); if (e == hipSuccess) e = hipStreamCreateWithPriority(&d->tail_stream, hipStreamNonBlocking, least); } }      // (the row rewrites there give way to the DP kernels of the first stream, and so does the remainder of a throughput level on its own stream)
         for (auto &ev : d->ev2) if (e == hipSuccess) e = hipEventCreate(&ev);
+        for (auto &ev : d->tail_ev) if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
         for (auto &ev : d->ev) if (e == hipSuccess) e = hipEventCreate(&ev);
         if (e != hipSuccess) { g_err = std::string("twl_init: ") + hipGetErrorString(e); return fail(TWL_ERR_HIP); }
     }
@@ -270,16 +278,19 @@ void twl_shutdown(void)
         (void)hipSetDevice(d->id);
         (void)hipStreamSynchronize(d->stream);
         (void)hipStreamSynchronize(d->stream2);
+        (void)hipStreamSynchronize(d->tail_stream);
         twl_level_pool_release(d);
         if (d->comm) { comm_destroy_raw(d->comm); d->comm = nullptr; }
         d->comm_send.release(); d->comm_recv.release();
-        for (Buf *b : {&d->cols, &d->tb, &d->gtb, &d->cells, &d->queue, &d->items, &d->errs, &d->dbg, &d->sim, &d->sim_off, &d->blk_off, &d->m24, &d->team, &d->simdump, &d->mt_chain, &d->mt_rec, &d->mt_seg, &d->mt_spath, &d->mt_stat, &d->mt_jobs, &d->mt_anchor, &d->gc_zero,
+        for (Buf *b : {&d->cols, &d->tb, &d->tb_tail, &d->gtb, &d->cells, &d->queue, &d->items, &d->errs, &d->dbg, &d->sim, &d->sim_off, &d->blk_off, &d->m24, &d->team, &d->simdump, &d->mt_chain, &d->mt_rec, &d->mt_seg, &d->mt_spath, &d->mt_stat, &d->mt_jobs, &d->mt_anchor, &d->gc_zero,
                        &d->h2d_freq, &d->h2d_gop, &d->h2d_gex, &d->h2d_len, &d->h2d_num, &d->d_aln, &d->d_alnlen, &d->d_err})
             b->release();
         for (auto &e : d->ev) if (e) (void)hipEventDestroy(e);
         if (d->stream) (void)hipStreamDestroy(d->stream);
         if (d->stream2) (void)hipStreamDestroy(d->stream2);
+        if (d->tail_stream) (void)hipStreamDestroy(d->tail_stream);
         for (auto &e : d->ev2) if (e) (void)hipEventDestroy(e);
+        for (auto &e : d->tail_ev) if (e) (void)hipEventDestroy(e);
         if (d->res_h) (void)hipHostFree(d->res_h);
         if (d->probe_h) (void)hipHostFree(d->probe_h);
         delete d;
@@ -595,6 +606,7 @@ int twl_set_knob(int key, int value)
     case TWL_KNOB_MT_LEAD2: if (value < 0) { g_mt_lead2 = 96; g_mt_lead2_lat = 128; } else g_mt_lead2 = g_mt_lead2_lat = std::max(16, value); return TWL_OK;
     case TWL_KNOB_PROT_CORRIDOR: g_prot_corridor = std::max(0, value); for (auto *d : g_devs) d->mem.forget_corridor(); return TWL_OK;      // (and forgets what earlier levels found)
     case TWL_KNOB_SCOUT_XDROP_PCT: g_scout_xdrop_pct = std::max(10, std::min(100, value)); return TWL_OK;
+    case TWL_KNOB_TAIL_OVERLAP: g_tail_overlap = value ? 1 : 0; return TWL_OK;
     case TWL_KNOB_THR_SMALL: g_thr_small = std::max(0, std::min(2, value)); for (auto *d : g_devs) d->mem.forget_small(); return TWL_OK;      // (and forgets what earlier levels found)
     default: g_err = "unknown knob"; return TWL_ERR_BAD_ARGUMENT;
     }

@@ -20,6 +20,7 @@ int g_force_global = 0;             // twl_set_knob(TWL_KNOB_FORCE_GLOBAL): ever
 int g_assume_onehot_query = 0;       // twl_set_knob(TWL_KNOB_ASSUME_ONEHOT_QUERY): the host form too takes the one-letter-query kernels
 int g_leaf_step = 1;                 // twl_set_knob(TWL_KNOB_LEAF_STEP): 0 = leaf x leaf levels too run the general step (talco_lean_kernel, SP 0; tests hold the two to each other)
 int g_poison_tb = 0;                 // twl_set_knob(TWL_KNOB_POISON_TB): the traceback scratch is filled with 0xFF bytes in front of every DP launch (tests: a word whose store was wrongly skipped then reads as garbage, not as the zeros of a fresh allocation)
+int g_tail_overlap = 1;              // twl_set_knob(TWL_KNOB_TAIL_OVERLAP): 1 = the tile-parallel remainder of a throughput level runs on a stream of its own beside the bulk launch (first_throughput), 0 = behind it on the call's stream
 // the knobs as the pure policy takes them (twl_policy.inc.hip)
 Knobs current_knobs()
 {

@@ -150,6 +150,9 @@ int launch_lean(Device *d, hipStream_t st, const twl::KArgs &base, const int32_t
     }
     a.simdump = DUMP ? (float *)d->simdump.p : nullptr;
     FILL_TRY(flush_fills(d, st));
+    // (the bulk of a throughput level whose remainder runs beside it: that stream waits for what is in front of this kernel -- the order, the arguments' uploads, the
+    // fills of the outputs -- and not for the kernel, behind which an event would complete only when the bulk has)
+    if (d->fork_next) { d->fork_next = false; HIP_TRY(hipEventRecord(d->tail_ev[0], st)); }
     hipLaunchKernelGGL((twl::talco_lean_kernel<P, W, RPL, MM, MINW, SPEC, DUMP, 0, SP>), dim3(grid), dim3(CfgT::THREADS), 0, st, a);
     HIP_TRY(hipGetLastError());
     if (SPEC && dbg_on()) {      // development: how often the guessed tile start was the true one
@@ -164,6 +167,15 @@ int launch_lean(Device *d, hipStream_t st, const twl::KArgs &base, const int32_t
     return TWL_OK;
 }
 
+// What a tile-parallel level launched beside a running bulk launch (first_throughput, Device::tail_side) may not share with it: the traceback scratch, which
+// ensure_tb may grow or poison, and the work counters -- a second block of kMtCounters behind the first in d->queue (run_device sizes the buffer for both
+// before anything is launched; 64 bytes in, so that the block is zeroed by the fill queue like the first).
+constexpr int kTailCounterBase = 16;
+static_assert(kTailCounterBase >= kMtCounters && (kTailCounterBase * sizeof(int32_t)) % 16 == 0, "the remainder's counters start behind the level's, 16-byte aligned");
+constexpr size_t kQueueBytes = (size_t)(kTailCounterBase + kMtCounters) * sizeof(int32_t);
+Buf &mt_tb(Device *d) { return d->tail_side ? d->tb_tail : d->tb; }
+int32_t *mt_counters(Device *d) { return (int32_t *)d->queue.p + (d->tail_side ? kTailCounterBase : 0); }
+
 // One launch of a tile-parallel kernel (MT 1 tiles / 2 scouts / 3 stitch) of geometry <W, RPL>; the caller has filled the NArgs.
 template <int P, int W, int RPL, int MM, int MINW, int MT, int SP = 0>
 int launch_mt_kernel(Device *d, hipStream_t st, twl::NArgs a, int n_items, int *grid_out = nullptr, size_t tb_groups = 0)
@@ -173,12 +185,18 @@ int launch_mt_kernel(Device *d, hipStream_t st, twl::NArgs a, int n_items, int *
     if ((rc = resident_per_cu<twl::talco_lean_kernel<P, W, RPL, MM, MINW, false, false, MT, SP>, CfgT::THREADS>(&blocks_per_cu))) return rc;
     int grid = std::max(1, std::min(n_items, d->num_cu * blocks_per_cu));
     // traceback words of a workgroup: up to the marker, or (pair scouts, MT 4) the tb_groups groups of a whole pair
-    const size_t tbw = tb_groups ? tb_groups * (size_t)CfgT::WINDOW : tb_words_for<CfgT>(a.marker);
+    // A scout (MT 2) keeps traceback words up to ITS marker, slot + 2 + mt_marg + lead anti-diagonals (talco_lean_kernel: spHi + mt_marg - scoutD0, at most kMaxMarker), which at a
+    // small marker of the level is the larger of the two: sized by the level's marker alone its words ran over into the next workgroup's (what a scout found then depended on
+    // its neighbours: predictions differed from run to run on the same level) and, behind the last workgroup, past the launch's share of the buffer.
+    int tbMarker = a.marker;
+    if constexpr (MT == 2) tbMarker = std::max(tbMarker, std::min(a.mt_slots + 2 + a.mt_marg + std::max(a.mt_lead, a.mt_lead2), twl::kMaxMarker));
+    const size_t tbw = tb_groups ? tb_groups * (size_t)CfgT::WINDOW : tb_words_for<CfgT>(tbMarker);
     if (tb_groups) grid = (int)std::max<size_t>(1, std::min<size_t>((size_t)grid, ((size_t)8 << 30) / (tbw * sizeof(uint32_t))));      // (at most 8 GB of them: fewer workgroups take the pairs in turn)
-    if ((rc = ensure_tb(d->tb, st, tbw, grid))) return rc;
-    a.tb = (uint32_t *)d->tb.p; a.tb_words = (int32_t)tbw; a.n_items = n_items;
+    Buf &tb = mt_tb(d);
+    if ((rc = ensure_tb(tb, st, tbw, grid))) return rc;
+    a.tb = (uint32_t *)tb.p; a.tb_words = (int32_t)tbw; a.n_items = n_items;
     // (every launch of a tile-parallel level has its own work counter: launch_mt zeroed the 16 of them in one go)
-    a.queue = (int32_t *)d->queue.p + (d->mt_launch++ % kMtCounters);
+    a.queue = mt_counters(d) + (d->mt_launch++ % kMtCounters);
     FILL_TRY(flush_fills(d, st));
     hipLaunchKernelGGL((twl::talco_lean_kernel<P, W, RPL, MM, MINW, false, false, MT, SP>), dim3(grid), dim3(CfgT::THREADS), 0, st, a);
     HIP_TRY(hipGetLastError());
@@ -221,7 +239,7 @@ int prepare_mt_tables(Device *d, hipStream_t st, const TilePlan &pl, const std::
     FILL_TRY(queue_fill(d, st, d->mt_spath.p, pl.spath_ints * sizeof(int32_t), 0xFE));
     FILL_TRY(queue_fill(d, st, d->mt_stat.p, pl.stat_bytes, 0));
     if (pl.anchors) FILL_TRY(queue_fill(d, st, d->mt_anchor.p, pl.anchor_ints * sizeof(int32_t), 0xFF));
-    FILL_TRY(queue_fill(d, st, d->queue.p, kMtCounters * sizeof(int32_t), 0));      // one work counter per launch: scouts + rounds x (tiles, stitch); launch_mt_kernel hands them out
+    FILL_TRY(queue_fill(d, st, mt_counters(d), kMtCounters * sizeof(int32_t), 0));      // one work counter per launch: scouts + rounds x (tiles, stitch); launch_mt_kernel hands them out
     d->mt_launch = 0;
     return TWL_OK;
 }

@@ -220,18 +220,39 @@ int first_throughput(Call &c, const NucPlan &pl, Ran &ran, int *grid, int *windo
     bool small = pl.small;
     int done = 0, rc;
     if (pl.probe && bulk >= 8 * d->num_cu && (rc = sample_small_window(c, pl, ran, grid, window, &small, &done))) return rc;
+    // The remainder beside the bulk (TWL_KNOB_TAIL_OVERLAP): the bulk's workgroups take one or two whole pairs each and end spread over the last milliseconds of the
+    // launch; the remainder's scouts and tile jobs, 0.15-2.3 ms each and handed out by a counter, take the slots they free.  The bulk is enqueued first, on the
+    // stream of higher priority; the remainder's stream starts from what is in front of the bulk kernel (launch_lean, fork_next) and the call's stream waits for its
+    // last launch before anything reads a result.  What the two would share and the bulk still uses is the remainder's own: Device::tail_side.
+    const bool beside = tail > 0 && g_tail_overlap != 0;
+    d->fork_next = beside;
     if (pl.four) rc = small ? launch_thr<4, 2, 5>(d, st, c.a, items + done, bulk - done, grid, window, pl.mm5, pl.sp)
                             : launch_thr<4, 3, 4>(d, st, c.a, items + done, bulk - done, grid, window, pl.mm5, pl.sp);
     else rc = with_mm<1, 0>(pl.mm, [&](auto MM) { return launch_lean<6, 8, 2, MM_OF(MM), 2>(d, st, c.a, items, bulk, grid, window); });
     // (after a sample that said no, its own pairs that outgrew 512 rows go straight on to the 1024-row window with the rest's)
     ran.start = small ? Level::From512 : (pl.four ? Level::From768 : Level::Mid);
+    const bool forked = beside && !d->fork_next;      // (the bulk kernel was launched with the fork event in front of it)
+    d->fork_next = false;
     if (rc || tail <= 0) return rc;
     const std::vector<int32_t> tailOrder(c.order.begin() + bulk, c.order.begin() + c.n_run);
     int g2 = 0, w2 = 0;
     ran.smallTiles = small && !ran.probed;
     ran.ranMt = true;
+    hipStream_t ts = forked ? d->tail_stream : st;
+    if (forked) HIP_TRY(hipStreamWaitEvent(d->tail_stream, d->tail_ev[0], 0));
+    d->tail_side = forked;
     // (one-letter query rows: the tiles too take the four-product form of the column score)
-    return with_mm<5, 2>(ran.mode, [&](auto MM) { return launch_mt<6, MM_OF(MM), 3, false, 4>(d, st, c.a, items + bulk, tailOrder, tail, c.h_len, &g2, &w2, ran.smallTiles, pl.sp); });
+    rc = with_mm<5, 2>(ran.mode, [&](auto MM) { return launch_mt<6, MM_OF(MM), 3, false, 4>(d, ts, c.a, items + bulk, tailOrder, tail, c.h_len, &g2, &w2, ran.smallTiles, pl.sp); });
+    d->tail_side = false;
+    if (!forked) return rc;
+    // the join, also behind a remainder that failed half way: what it did launch is waited for before the call returns its error and a buffer is touched again
+    if (!rc) rc = flush_fills(d, ts);
+    else d->fills.n = 0;
+    if (hipEventRecord(d->tail_ev[1], ts) != hipSuccess || hipStreamWaitEvent(st, d->tail_ev[1], 0) != hipSuccess) {
+        (void)hipStreamSynchronize(ts);
+        if (!rc) { g_err = "the join of a level's remainder with its bulk launch failed"; rc = TWL_ERR_HIP; }
+    }
+    return rc;
 }
 
 // Step 3, nucleotide: the first launch plan_nucleotide names.
@@ -412,7 +433,7 @@ int run_device(Device *d, hipStream_t st, const twl_params *p, int32_t n_pairs, 
     int rc;
     if (!d_packed && (rc = d->cols.ensure((size_t)n_pairs * 2 * (size_t)seq_len * (size_t)(p->P + 2) * sizeof(float)))) return rc;
     if ((rc = d->cells.ensure((size_t)n_pairs * sizeof(unsigned long long)))) return rc;
-    if ((rc = d->queue.ensure(64))) return rc;
+    if ((rc = d->queue.ensure(kQueueBytes))) return rc;      // (both blocks of work counters, before anything is launched: never reallocated under a running kernel)
     if ((rc = d->items.ensure((size_t)n_pairs * sizeof(int32_t)))) return rc;
     Call c{d, st, p, n_pairs, seq_len, d_len, d_num, d_alnlen, d_err, h_len};
     if ((rc = order_pairs(c))) return rc;

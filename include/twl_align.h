@@ -148,7 +148,7 @@ int twl_column_scores(const twl_params *p, int32_t seq_len, const float *freq, c
 int twl_dp_column_scores(const twl_params *p, int32_t seq_len, const float *freq, const float *gap_open, const float *gap_extend,
                          const int32_t *len, const int32_t *num, float *out);
 
-/* Diagnostics: the tables of the LAST tile-parallel level on `device` (talco_nuc.hip.h: anchors, scouts, chain, tile jobs, stitch), as that level left
+/* Diagnostics: the tables of the LAST tile-parallel level on `device` (talco_mt.hip.h, talco_nuc.hip.h: anchors, scouts, chain, tile jobs, stitch), as that level left
    them.  Read-only: the call takes the device's lock, waits for the device's stream and copies device buffers to the host; it launches no kernel and changes
    no knob.  Rows of every table are positions in the level's launch, order[row] is the pair of a row.  A table pointer may be NULL (not copied); a first
    call with only `dims` tells the sizes:

@@ -1,8 +1,8 @@
-"""Directed inputs for the fast division of the lean DP kernels (fast_div, talco_nuc.hip.h) at the corners of its guard.
+"""Directed inputs for the fast division of the lean DP kernels (fast_div, talco_div.hip.h) at the corners of its guard.
 
 The three guards, as the code states them:
 
-* a profile entry is zero or 2^-20 <= |x| <= 2^30 (div_guard_bad, talco_nuc.hip.h);
+* a profile entry is zero or 2^-20 <= |x| <= 2^30 (div_guard_bad, talco_div.hip.h);
 * the denominator float(refNum) * float(qryNum) lies in [1, 2^40] (talco_lean_kernel, in front of the first tile);
 * every score of the matrix and gap_char are zero or within [2^-10, 2^10] (fast_div_in_range, twl_policy.inc.hip).
 

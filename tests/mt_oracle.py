@@ -1,6 +1,6 @@
 """Restatements of the host plan and of the two small kernels of a tile-parallel level, in numpy.  Test infrastructure only.
 
-Written from DESIGN.md section 3.3 and the comments of twilight_amd/csrc/talco_nuc.hip.h (the block "tile-parallel alignment", "anchored scouts") and of
+Written from DESIGN.md section 3.3 and the comments of twilight_amd/csrc/talco_mt.hip.h (the block "tile-parallel alignment", "anchored scouts") and of
 twl_policy.inc.hip (plan_tile_level), one definition at a time; the DP itself is not restated here -- tiles come from the oracle (oracle_lib.tile_from).
 
   launch_order   the pairs that run, longest first

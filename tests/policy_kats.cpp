@@ -29,7 +29,7 @@ static std::string climb(const Ran &ran, int count, long long sumLen, bool guard
 }
 static Ran nuc(Level start, bool leanMid = true, int mode = 2) { Ran r; r.start = start; r.leanMid = leanMid; r.mode = mode; return r; }
 
-// The plan and the job table of a tile-parallel level at marker 128, sequence capacity 300 (slots = 600 / 127 + 2 = 6: line 228), 12-word tile records (kMtRec, talco_nuc.hip.h).
+// The plan and the job table of a tile-parallel level at marker 128, sequence capacity 300 (slots = 600 / 127 + 2 = 6: line 228), 12-word tile records (kMtRec, talco_mt.hip.h).
 struct Tiles { TilePlan pl; std::vector<int32_t> jobs; };
 static Tiles tiles(const std::vector<int32_t> &order, const std::vector<int32_t> &len, const Knobs &k, bool wide = false, bool can_small = false, bool small_tiles = false)
 {

@@ -90,6 +90,23 @@ def test_product_does_not_reference_oracle():
                 assert "oracle_lib" not in text and "libtwl_oracle" not in text and "talco_oracle" not in text, f
 
 
+def test_lean_kernel_headers_compile_on_their_own(tmp_path):
+    """The headers talco_nuc.hip.h was split into by concern each include what they use: a file that holds nothing but the #include passes the
+    device-side syntax check, with the product's -std and -I.  And each is part of the library's source stamp."""
+    import subprocess
+
+    import __graft_entry__ as g
+
+    std = [f for f in g.HIP_FLAGS if f.startswith("-std=")]
+    assert std
+    for header in ("talco_lds.hip.h", "talco_div.hip.h", "talco_team.hip.h", "talco_mt.hip.h"):
+        assert header in g.KERNEL_SOURCES, header
+        src = tmp_path / (header.split(".")[0] + "_alone.hip")
+        src.write_text('#include "%s"\n' % header)
+        r = subprocess.run([g.HIPCC, "--offload-arch=gfx950", "--cuda-device-only", "-fsyntax-only"] + std + ["-I" + g.CSRC, str(src)], capture_output=True, text=True)
+        assert r.returncode == 0, (header, r.stderr[-2000:])
+
+
 def test_forked_cli_leaves_nobody_behind_when_a_rank_fails(built, tmp_path):
     """twilight-mi355x --gpu-index a,b,c forks one process per GPU before anything touches a device.  On a box without those devices rank 0 fails in
     twl_init -- the children, which wait on the shared page for the communicator id, must end too (they used to spin for ever)."""

@@ -1,4 +1,4 @@
-"""The fast division of the lean DP kernels (fast_div, talco_nuc.hip.h) at the corners of its guard, on every route (-m gpu).
+"""The fast division of the lean DP kernels (fast_div, talco_div.hip.h) at the corners of its guard, on every route (-m gpu).
 
 The inputs come from tests/div_cases.py; tests/test_div_edge_inputs_cpu.py holds each of them to what it claims.
 

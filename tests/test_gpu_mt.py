@@ -1,4 +1,4 @@
-"""Tile-parallel alignment (talco_nuc.hip.h, MT kernels: scouts -> chain -> tiles -> stitch) vs the oracle, through the C ABI (-m gpu).
+"""Tile-parallel alignment (talco_mt.hip.h and the MT kernels of talco_nuc.hip.h: scouts -> chain -> tiles -> stitch) vs the oracle, through the C ABI (-m gpu).
 
 Levels with few pairs of many tiles each run all tiles of all pairs side by side from PREDICTED start cells; the stitch launch keeps a
 tile only when its true start equals the predicted one and computes it in line otherwise, so paths, error codes and band cells must be

@@ -1,4 +1,4 @@
-"""The tile-parallel kernels (talco_nuc.hip.h: mt_anchor_kernel, the MT 2 scouts, mt_chain_kernel, the MT 1 tile jobs, the MT 3 stitch; launch_mt /
+"""The tile-parallel kernels (talco_mt.hip.h: mt_anchor_kernel, mt_chain_kernel; talco_nuc.hip.h: the MT 2 scouts, the MT 1 tile jobs, the MT 3 stitch; launch_mt /
 plan_tile_level on the host) where anchors, chain and records switch (-m gpu).
 
 tests/test_gpu_mt.py holds whole levels to the oracle.  Here every case of tests/mt_cases.py (tests/test_mt_edge_inputs_cpu.py proves, without a GPU, that each

@@ -1,6 +1,7 @@
 """Timing experiments on copies of the library built with an experiment flag (-DTWL_EXP_SALU / -DTWL_EXP_VALU: 24 extra scalar / vector
 instructions per wave and diagonal): what does a wide level and a lone pair cost then?  (The convergence-test experiment this script was
-written for led to the pre-test of DESIGN.md section 3.1.)
+written for led to the pre-test of DESIGN.md section 3.1.)  The -DTWL_EXP_* switches are not in the product source: `git apply tools/exp/step_switches.patch` first
+(tools/exp/README.md); without it such a flag builds the product kernel.
     python tools/exp_step_cost.py [base | TWL_EXP_SALU | TWL_EXP_VALU | <label> <compiler flags...>]        (GPU box; does not touch the product library;
     prints a checksum of the paths so that a flag experiment can be compared with the base build)"""
 import os, subprocess, sys, tempfile, time

@@ -1,7 +1,9 @@
 """Development aid: compile ONE talco_lean_kernel instantiation to gfx950 assembly (seconds, no GPU) and report its registers, scratch, LDS, and the scratch /
 spill traffic inside its diagonal loops (loop depth >= 3: a reload there sits on every anti-diagonal's critical path).
 
-    python tools/kernel_check.py "<6, 4, 2, 2, 5, false, false, 0>" [more instantiations ...]      ->  one line each; the listing stays in /tmp/twl_kc_<tag>.s"""
+    python tools/kernel_check.py "<6, 4, 2, 2, 5, false, false, 0>" [more instantiations ...]      ->  one line each; the listing stays in /tmp/twl_kc_<tag>.s
+
+Whether a change moved any instruction of any kernel of the library: tools/isa_compare.py (two source trees, text against text)."""
 import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "twilight_amd", "csrc")

@@ -1,5 +1,7 @@
 """Development aid: a lone pair / a few pairs through the tile-parallel path on either geometry of its tile launches (TWL_KNOB_MT_THR_JOBS).
-   python tools/lone_pair_probe.py <pairs> <length> <thr_jobs> [library.so]"""
+   python tools/lone_pair_probe.py <pairs> <length> <thr_jobs> [library.so]
+A library.so with another latency geometry (-DTWL_EXP_LAT_W=<waves> -DTWL_EXP_LAT_RPL=<blocks per wave>, tools/build_exp.sh) needs the switch, which is not in the
+product source: `git apply tools/exp/step_switches.patch` first (tools/exp/README.md)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

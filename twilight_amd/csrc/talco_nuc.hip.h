@@ -18,18 +18,28 @@
 //     stale slot loses by construction; slots alternate by parity;
 //   * the running maximum / X-drop threshold live in (uniform) vector registers: no scalar float emulation through integer keys;
 //   * q[m]*M[l][m] (first rounding of (q*M)*r, :386) kept per row for the whole tile; the IEEE division by refNum*qryNum
-//     (:444) as the hoisted-reciprocal form of the same correctly rounded sequence (see fast_div below);
+//     (:444) as the hoisted-reciprocal form of the same correctly rounded sequence (fast_div, talco_div.hip.h);
 //   * the traceback word of a row block is stored every 8th diagonal unconditionally (no dirty tracking).
 // Everything observable (band evolution, tile boundaries, paths, error codes, band-cell counts) is unchanged and is checked
 // against the oracle by the same parity suite.
+//
+// This file holds the kernel alone; what it stands on is in talco_lds.hip.h, talco_div.hip.h, talco_team.hip.h and talco_mt.hip.h.  talco_lean_kernel is ONE
+// function on purpose (every extraction tried moved instructions in the diagonal loops); its sections, by the numbers in their comments:
+//   1  job setup       169-294     the next pair off the queue, start cell, records of earlier tile-parallel launches
+//   2  tile setup      295-534     where the tile starts; 2.1 per-slot state and the loaders (354); 2.2 the band bookkeeping (480)
+//   3  step            535-950     one diagonal: 3.1 loads (601), 3.2 column score (617), 3.3 neighbours, recurrence (733), 3.4 pointers (769), 3.5 reductions (793), 3.6 post (839)
+//   4  phase driver    951-1079    phases A, B, C on the step; speculative start: poll and settle; the scout's end
+//   5  tile exit       1080-1131   the cell the tile ends in, the next tile's start
+//   6  walk            1132-1246   traceback from that cell, the segment into the output (tile jobs: the record; scouts: the path samples)
+//   7  job end         1247-1302   verdict, length, band cells; records and counters of the tile-parallel launches
 #pragma once
 #include "talco_kernel.hip.h"
+#include "talco_lds.hip.h"       // LDS loads / stores / atomics at register addresses, wg_barrier_lds
+#include "talco_div.hip.h"       // fast_div, refined_rcp, div_guard_bad
+#include "talco_team.hip.h"      // the mailbox of the speculative tile start (SPEC)
+#include "talco_mt.hip.h"        // tile-parallel alignment (MT): the design note, kMtRec, mt_chain_kernel, the scouts' start cells, mt_anchor_kernel
 
-#if defined(TWL_EXP_NOPRIO)      // experiment builds: no wave priorities
-#define TWL_SETPRIO(x) do {} while (0)
-#else
 #define TWL_SETPRIO(x) __builtin_amdgcn_s_setprio(x)
-#endif
 
 namespace twl {
 
@@ -61,7 +71,7 @@ struct NArgs {
     const long long *sim_off;
     unsigned long long *team; // speculative tile start (SPEC kernels): [n_items][16] mailbox words, zeroed by the host
     float *simdump;           // DUMP kernels (diagnostics, one pair): [Q][R] column scores as the DP evaluated them
-    // tile-parallel alignment (MT kernels, see below)
+    // tile-parallel alignment (MT kernels, see talco_mt.hip.h)
     const int32_t *mt_jobs;   // [n_items][3] {pair, slot, row of the pair in the mt_* tables} (MT 1, 2; `items` is unused there)
     int32_t *mt_chain;        // [row][mt_slots][2]  (row = the pair's position in the stitch launch) predicted start {ref_idx, qry_idx} of tile `slot`; ref_idx < 0: unknown
     int32_t *mt_rec;          // [row][mt_slots][kMtRec] result of the tile that was run from the predicted start
@@ -75,284 +85,6 @@ struct NArgs {
     int32_t mt_inline;        // MT 3: 1 = a tile without a matching record is computed in line (last round); 0 = the pair is suspended there
 };
 
-typedef float nuc_f4 __attribute__((ext_vector_type(4)));
-typedef float nuc_f2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ float4 lds_ld128(unsigned addr)      // one ds_read_b128 at a byte address kept in a register
-{
-    const nuc_f4 v = *reinterpret_cast<const __attribute__((address_space(3))) nuc_f4 *>((const __attribute__((address_space(3))) char *)nullptr + addr);
-    return make_float4(v.x, v.y, v.z, v.w);
-}
-typedef int nuc_i2 __attribute__((ext_vector_type(2)));
-typedef int nuc_i4 __attribute__((ext_vector_type(4)));
-template <class T>
-__device__ __forceinline__ T lds_ld(unsigned addr)
-{
-    return *reinterpret_cast<const __attribute__((address_space(3))) T *>((const __attribute__((address_space(3))) char *)nullptr + addr);
-}
-template <class T>
-__device__ __forceinline__ void lds_st(unsigned addr, T v)
-{
-    *reinterpret_cast<__attribute__((address_space(3))) T *>((__attribute__((address_space(3))) char *)nullptr + addr) = v;
-}
-template <int OFF>
-__device__ __forceinline__ void lds_max_u32_off(unsigned addr, unsigned v) { asm volatile("ds_max_u32 %0, %1 offset:%2" ::"v"(addr), "v"(v), "n"(OFF) : "memory"); }
-template <int OFF>
-__device__ __forceinline__ void lds_max_f32_off(unsigned addr, float v) { asm volatile("ds_max_f32 %0, %1 offset:%2" ::"v"(addr), "v"(v), "n"(OFF) : "memory"); }
-// ds atomics on (address register + immediate offset)
-#define TWL_LDS_ATOM(NAME)                                                                                                     \
-    template <int OFF>                                                                                                         \
-    __device__ __forceinline__ void NAME##_off(unsigned addr, int v) { asm volatile(#NAME " %0, %1 offset:%2" ::"v"(addr), "v"(v), "n"(OFF) : "memory"); }
-TWL_LDS_ATOM(ds_min_i32)
-TWL_LDS_ATOM(ds_max_i32)
-TWL_LDS_ATOM(ds_or_b32)
-#undef TWL_LDS_ATOM
-// Workgroup barrier that waits for this wave's LDS traffic only.  __syncthreads() also drains the vector-memory counter, which
-// makes every eighth diagonal wait for the round trip of its traceback store; those stores are only read after the tile's
-// final __syncthreads().
-__device__ __forceinline__ void wg_barrier_lds() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-__device__ __forceinline__ void lds_max_u32(unsigned addr, unsigned v) { asm volatile("ds_max_u32 %0, %1" ::"v"(addr), "v"(v) : "memory"); }
-__device__ __forceinline__ void lds_max_f32(unsigned addr, float v) { asm volatile("ds_max_f32 %0, %1" ::"v"(addr), "v"(v) : "memory"); }
-
-// n / d for a divisor that is fixed for the whole pair.  `r` is the refined reciprocal fma(fma(-d, rcp(d), 1), rcp(d), rcp(d)).
-// This is the instruction sequence the compiler emits for an IEEE fp32 division (v_div_scale, v_rcp, 4 fma, v_div_fmas,
-// v_div_fixup) with the parts that depend on d alone hoisted and the scaling steps left out.  v_div_scale rescales only when
-// d or n/d is near the ends of the exponent range or |n| < 2^-103, and v_div_fixup only patches zeros, infinities and NaNs,
-// so for 1 <= d <= 2^40 and n == 0 or 2^-73 <= |n| <= 2^80 both give the same bits (a zero quotient may differ in sign, which
-// no comparison or sum downstream can see).  Three guards keep the kernels inside that range: a profile entry is zero or
-// 2^-20 <= |x| <= 2^30 (div_guard_bad below), the denominator float(refNum) * float(qryNum) lies in [1, 2^40] (talco_lean_kernel,
-// in front of the first tile), every score and gap_char is zero or within [2^-10, 2^10] (fast_div_in_range, twl_policy.inc.hip:
-// anything else plans the IEEE-division kernels from the start).  The smallest non-zero product inside them is 2^-50, whose ulp
-// is the 2^-73 above.  A pair outside the first two ends with err = kErrGuard and is re-run on the IEEE-division kernel
-// (climb_ladder, Rung::Guard); a tile that also outgrew its window reports that first.  tests/test_gpu_div_edges.py compares the
-// two forms bit for bit on device, through the DUMP instantiation of talco_lean_kernel, with operands on every one of these limits.
-__device__ __forceinline__ float fast_div(float n, float d, float r)
-{
-    const float q0 = n * r;
-    const float t0 = __builtin_fmaf(-d, q0, n);
-    const float q1 = __builtin_fmaf(t0, r, q0);
-    const float t1 = __builtin_fmaf(-d, q1, n);
-    return __builtin_fmaf(t1, r, q1);
-}
-__device__ __forceinline__ float refined_rcp(float d)
-{
-    const float r0 = __builtin_amdgcn_rcpf(d);
-    const float e = __builtin_fmaf(-d, r0, 1.0f);
-    return __builtin_fmaf(e, r0, r0);
-}
-// a profile entry fast_div's guard accepts: zero, or 2^-20 <= |x| <= 2^30
-__device__ __forceinline__ bool div_guard_bad(float x)
-{
-    const float ax = __builtin_fabsf(x);
-    return (x != 0.0f) && !(ax >= 9.5367431640625e-07f && ax <= 1073741824.0f);
-}
-
-// ---- speculative tile start (SPEC = true) ----
-// A tile runs ~1450 diagonals: 1024 up to the marker and ~420 more until every surviving cell agrees on the cell of the marker
-// diagonal all paths run through (TALCO-XDrop.cpp:585-612); the next tile starts there with scores at zero (:615-655, :77-106), so it
-// depends on the POSITION of that cell only.  With fewer pairs than compute units, two workgroups work on one pair: they take the tiles
-// in turn, and the one whose turn is next starts as soon as the other reaches its marker, from the best-scoring cell of the marker
-// diagonals (the guess).  When the running tile has converged its workgroup publishes the true position: the partner carries on if the
-// guess was right and restarts from the true position otherwise -- a wrong guess costs nothing but the idle workgroup's time, and
-// the result is the same either way.  Mailbox words (global memory, one 8-byte agent-scope atomic each, tag = tile + 1):
-//   guess[t & 3], truth[t & 3] = tag:16 | flags:16 | ref_idx:16 | qry_idx:16      pos[t & 3] = tag:16 | 0:16 | output offset:32
-constexpr unsigned kTeamLast = 1u, kTeamErr = 2u;
-constexpr int kTeamWords = 16, kTeamGuess = 0, kTeamTruth = 4, kTeamPos = 8, kTeamStat = 12;
-__device__ __forceinline__ unsigned long long team_word(unsigned tag, unsigned flags, unsigned hi, unsigned lo)
-{
-    return ((unsigned long long)(tag & 0xFFFFu) << 48) | ((unsigned long long)(flags & 0xFFFFu) << 32) | ((unsigned long long)(hi & 0xFFFFu) << 16) | (lo & 0xFFFFu);
-}
-__device__ __forceinline__ unsigned long long team_load(const unsigned long long *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void team_store(unsigned long long *p, unsigned long long v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// one lane waits (bounded: ~2 s) until the word carries the tag; 0 = gave up: the partner is not co-resident or far too slow (a GPU
-// shared with another process, a profiler serialising the workgroups).  That is a scheduling condition, not an alignment error: the
-// caller reports the internal re-run code (kErrOverflow), the host re-runs the pair on the plain kernel of the next stage
-__device__ __forceinline__ unsigned long long team_wait(const unsigned long long *p, unsigned tag, const unsigned long long *alt = nullptr)
-{
-    for (int spin = 0; spin < (1 << 21); ++spin) {
-        const unsigned long long v = team_load(p);
-        if ((unsigned)(v >> 48) == tag) return v;
-        if (alt) { const unsigned long long u = team_load(alt); if ((unsigned)(u >> 48) == tag) return u | (1ull << 47); }      // bit 47: "this is the guess"
-        __builtin_amdgcn_s_sleep(16);
-    }
-    return 0ull;
-}
-// order-preserving key of a score for an integer maximum (the guess only: never part of a result)
-__device__ __forceinline__ unsigned score_key(float f)
-{
-    const unsigned b = (unsigned)__float_as_int(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
-// ---- tile-parallel alignment (MT != 0) ----
-// A tile is a pure function of its start cell (TALCO-XDrop.cpp:77-93: Tile() reads reference_idx / query_idx and `tile == 0`, nothing else
-// of the previous tile), and every tile after the first advances ref_idx + qry_idx by marker or marker - 1 (:616-619).  So if the start
-// cells of all tiles of a pair were known, the tiles could run side by side on as many compute units.  They can be PREDICTED: a DP that
-// starts a few hundred anti-diagonals before a tile boundary, from a cell merely NEAR the optimal path, runs into that path (the band
-// opens by a row per diagonal, the X-drop keeps everything within `xdrop` of the best cell) and from there on its traceback path IS the
-// optimal path.  Four launches per level:
-//   MT 2  scouts   one workgroup per (pair, tile boundary t): a short tile from the cell of anti-diagonal (marker-1)*t - 1 - lead that lies on
-//                  the straight line between the corners, stopped right after its own marker (placed mt_marg diagonals behind the boundary
-//                  range), traced back from the better of the best cells of its two marker diagonals; writes where its path crosses the
-//                  anti-diagonals [(marker-1)*t - 1, marker*t + 1] into mt_spath
-//   MT 4  pair scout  one workgroup per pair (wide re-runs, round 4): the DP from (0, 0) to the last anti-diagonal with every traceback word kept, no
-//                  marker and no convergence test; its path from the end cell gives mt_spath for ALL anti-diagonals.  For pairs whose tiles do not
-//                  converge (diffuse profiles: every tile runs to the end of the pair and its successor starts where the path from the END cell
-//                  crosses the marker diagonal) a local scout cannot know that path; the suffix of the pair's global path does
-//   (mt_chain_kernel: walks mt_spath from (0, 0): start of tile t = the path cell on diagonal s + marker, or on s + marker - 1 when the
-//                  path steps over that diagonal -- the reference's state 3, :520-524)
-//   MT 1  tiles    one workgroup per (pair, tile): the tile from the predicted start, result + path segment into mt_rec / mt_seg
-//   MT 3  stitch   one workgroup per pair runs the ordinary tile loop; a tile whose TRUE start equals the start a record was computed
-//                  from takes the record (same function, same argument), any other tile is computed in line as always.
-// A wrong prediction that also gets the anti-diagonal wrong (marker vs marker - 1) would shift every later boundary of the pair, so the
-// chain / tiles / stitch launches run in ROUNDS: a stitch launch that is not the last one suspends a pair at the first tile without a
-// matching record (mt_front), the next chain launch re-derives the pair's remaining starts from that TRUE cell, the next tile launch runs
-// the tiles whose record does not match the new prediction; the last stitch launch computes whatever is still missing in line.
-// Results are those of the plain loop by construction; predictions only decide how much of it is already done.
-constexpr int kMtRec = 12;     // {1 = valid / 2 = the job failed, start ref, start qry, next ref, next qry, last_tile, segment bytes, tail dir, tail len, band cells, error code of a failed job, its window rows}
-
-// start cells of all tiles of a pair from the scouts' path samples (one thread per pair)
-__global__ void mt_chain_kernel(const int32_t *spath, int sp_pitch, const int32_t *len, const int32_t *items, int n_items, int32_t *chain, int slots,
-                                int marker, int perturb, const int32_t *front)
-{
-    const int it = blockIdx.x * blockDim.x + threadIdx.x;
-    if (it >= n_items) return;
-    const int pair = items[it];
-    const int R = len[2 * pair], Q = len[2 * pair + 1];
-    // (the tables of a tile-parallel level are indexed by the pair's position in the launch, not by its id: they cost memory and fills for the pairs that run only)
-    const int32_t *sp = spath + (size_t)it * (size_t)sp_pitch;
-    int32_t *ch = chain + (size_t)it * (size_t)slots * 2;
-    const int32_t *fr = front + (size_t)it * 8;
-    if (fr[0] == 2) return;                       // the pair is finished
-    int s = 0, t = 1;
-    if (fr[0] == 1) {                             // later rounds: from the true start of the first tile without a record
-        t = fr[1];
-        if (t >= slots) return;
-        ch[2 * t] = fr[2]; ch[2 * t + 1] = fr[3];
-        s = fr[2] + fr[3];
-        t += 1;
-    } else { ch[0] = 0; ch[1] = 0; }
-    for (; t < slots; ++t) {
-        const int d = s + marker;
-        if (d > R + Q - 2) break;
-        int q = sp[d];
-        if (q >= 0) s = d;
-        else if (q == -1 && d - 1 > s && sp[d - 1] >= 0) { q = sp[d - 1]; s = d - 1; }
-        else break;
-        int r = s - q;
-        // development / test aid: spoil every perturb-th prediction, so that the stitch kernel has tiles to compute in line
-        if (perturb > 0 && (t % perturb) == 0) { if (q > 0 && r + 1 < R) { q -= 1; r += 1; } else if (r > 0 && q + 1 < Q) { q += 1; r -= 1; } }
-        if (r < 0 || r >= R || q >= Q) break;
-        ch[2 * t] = r; ch[2 * t + 1] = q;
-    }
-    for (; t < slots; ++t) { ch[2 * t] = -1; ch[2 * t + 1] = -1; }
-}
-
-// ---- anchored scouts (round 5) ----
-// A scout needs its long lead (320 anti-diagonals) because the straight line between the corners is up to ~55 rows off the path on the families
-// measured: the band has to open that far before the scout can run into the path.  Where the path IS can be read off the profiles before any DP: around
-// the cell of the straight line the consensus letters of the two profiles agree on one diagonal offset and on no other (tests/study/tile_predict_study.c:
-// +-32 columns, offsets -128..127).  mt_anchor_kernel finds that offset for every tile boundary; a scout whose anchor is trusted -- or lies between two
-// trusted ones that agree (the path drifts by a few rows per tile; an offset that jumps is a long indel and says nothing about its neighbours) -- starts
-// from the anchored cell only mt_lead2 (96) anti-diagonals ahead.  On the 154 pairs of levels 15-31 of 10 000 x 10 kbp (the CPU study, with the nine windows of
-// mt_anchor_kernel): all but 2 of 3080 boundaries anchored, 3078 true starts found against 3079 with the long lead, 61 % fewer scout diagonals; on the device the scouts of a
-// pass 39 -> 15 ms.  Predictions only: a wrong anchor costs what any wrong prediction costs -- a second round of its level.
-constexpr int kAnchorHalf = 32, kAnchorOffsets = 256, kAnchorNear = 3, kAnchorJump = 12;
-constexpr int kAnchorMinMatches = 36, kAnchorMinGap = 8;      // trusted: >= 55 % of the 64 columns agree and the best other offset (not a neighbour) is >= 12 % behind
-
-// the cell of anti-diagonal d0 on the straight line between the corners (false: none)
-__device__ __forceinline__ bool scout_line_cell(int d0, int R, int Q, int &r, int &q)
-{
-    q = (int)(((long long)d0 * Q) / (R + Q));
-    q = min(q, Q - 1);
-    r = d0 - q;
-    if (r > R - 1) { r = R - 1; q = d0 - r; }
-    return !(q > Q - 1 || r < 0);
-}
-// the anchor of boundary `slot` of a pair from the table of its row: its own when trusted, else between two trusted neighbours that agree
-__device__ __forceinline__ bool scout_anchor(const int32_t *an, int slot, int slots, int &o)
-{
-    const int w = __builtin_amdgcn_readfirstlane(an[slot]);
-    if (w >= 0) { o = w - 128; return true; }
-    int l = -1, r = -1, ol = 0, orr = 0;
-    for (int u = 1; u <= kAnchorNear; ++u) {
-        if (l < 0 && slot - u >= 1) { const int v = __builtin_amdgcn_readfirstlane(an[slot - u]); if (v >= 0) { l = slot - u; ol = v - 128; } }
-        if (r < 0 && slot + u < slots) { const int v = __builtin_amdgcn_readfirstlane(an[slot + u]); if (v >= 0) { r = slot + u; orr = v - 128; } }
-    }
-    if (l < 0 || r < 0 || abs(orr - ol) > kAnchorJump * (r - l)) return false;
-    o = ol + (orr - ol) * (slot - l) / (r - l);
-    return true;
-}
-// the anchored start cell on anti-diagonal d0: q - r moved by o (rounded away from zero to an even step)
-__device__ __forceinline__ bool scout_anchored_cell(int d0, int R, int Q, int o, int &r, int &q)
-{
-    int r0, q0;
-    if (!scout_line_cell(d0, R, Q, r0, q0)) return false;
-    q = q0 + (o >= 0 ? (o + 1) / 2 : -((-o + 1) / 2));
-    r = d0 - q;
-    if (q < 0) { q = 0; r = d0; }
-    if (r < 0) { r = 0; q = d0; }
-    return q < Q && r < R;
-}
-
-// one workgroup of 256 threads per scout job {pair, slot, row}: thread t counts the columns i in [-32, 32) with consensus(ref, r0 + i) == consensus(qry, q0 + i + t - 128),
-// first in the window around the straight line's cell, then -- until one is trusted -- in windows moved along the diagonal by +24, -24, +48, ... -96 columns (the path's
-// offset is the same a few columns on unless an indel lies between; the top 52 pairs of 10 000 x 10 kbp: 18 % of the boundaries without an anchor with the one window, 0.2 % with the nine)
-constexpr int kAnchorShift = 24, kAnchorShifts = 4, kAnchorPad = kAnchorShift * kAnchorShifts;
-template <int P>
-__global__ __launch_bounds__(256) void mt_anchor_kernel(const float *cols, const int32_t *len, int seq_len, const int32_t *jobs, int n_jobs, int32_t *anchor, int slots, int marker, int lead2)
-{
-    static_assert(kAnchorOffsets == 256 && 2 * kAnchorHalf + 2 * kAnchorPad == 256, "one thread per offset, one per staged reference letter");
-    __shared__ unsigned char s_r[2 * kAnchorHalf + 2 * kAnchorPad], s_q[2 * kAnchorHalf + 2 * kAnchorPad + kAnchorOffsets];
-    __shared__ int s_cnt[kAnchorOffsets], s_done;
-    const int job = blockIdx.x;
-    if (job >= n_jobs) return;
-    const int pair = jobs[3 * job], slot = jobs[3 * job + 1], row = jobs[3 * job + 2];
-    const int R = len[2 * pair], Q = len[2 * pair + 1];
-    const int spLo = (marker - 1) * slot - 1;
-    const int d0 = max(spLo - lead2, 0);
-    int r0, q0;
-    if (spLo > R + Q - 2 || R < 2 || Q < 2 || !scout_line_cell(d0, R, Q, r0, q0)) return;      // (the table is filled with -1)
-    // consensus letter of a column: the most frequent of A, C, G, T (of the twenty amino acids) when it is at least as frequent as the gap; else a letter that matches nothing
-    auto letter = [&](int side, int col, int n) -> unsigned char {
-        if (col < 0 || col >= n) return (unsigned char)(100 + side);
-        const float *pf = cols + (((size_t)pair * 2 + side) * (size_t)seq_len + col) * (P + 2);
-        int best = 0; float bc = pf[0];
-        for (int j = 1; j < P - 2; ++j) if (pf[j] > bc) { bc = pf[j]; best = j; }
-        return (bc > 0.0f && bc >= pf[P - 1]) ? (unsigned char)best : (unsigned char)(100 + side);
-    };
-    const int t = threadIdx.x;
-    s_r[t] = letter(0, r0 - kAnchorHalf - kAnchorPad + t, R);
-    for (int u = t; u < 2 * kAnchorHalf + 2 * kAnchorPad + kAnchorOffsets; u += 256) s_q[u] = letter(1, q0 - kAnchorHalf - kAnchorPad - kAnchorOffsets / 2 + u, Q);
-    if (t == 0) s_done = 0;
-    __syncthreads();
-    for (int sh = 0; sh <= 2 * kAnchorShifts; ++sh) {
-        const int base = kAnchorPad + ((sh == 0) ? 0 : ((sh & 1) ? kAnchorShift * ((sh + 1) / 2) : -kAnchorShift * (sh / 2)));
-        int c = 0;
-        for (int i = 0; i < 2 * kAnchorHalf; ++i) c += (s_r[base + i] == s_q[base + i + t]) ? 1 : 0;      // offset o = t - 128
-        s_cnt[t] = c;
-        __syncthreads();
-        if (t < 64) {
-            // the best offset: most matches, ties to the smallest |o|, the negative one first (the order 0, -1, 1, -2, 2, ... of the study)
-            int key = -1;
-            for (int u = t; u < kAnchorOffsets; u += 64) {
-                const int o = u - kAnchorOffsets / 2;
-                const int rank = (o == 0) ? 0 : (o < 0 ? -2 * o - 1 : 2 * o);
-                key = max(key, (s_cnt[u] << 16) | (0xFFFF - rank));
-            }
-            for (int m = 32; m >= 1; m >>= 1) key = max(key, __shfl_xor(key, m, 64));
-            const int rank = 0xFFFF - (key & 0xFFFF);
-            const int bo = (rank == 0) ? 0 : ((rank & 1) ? -(rank + 1) / 2 : rank / 2);
-            int second = -1;
-            for (int u = t; u < kAnchorOffsets; u += 64) if (abs(u - kAnchorOffsets / 2 - bo) > 2) second = max(second, s_cnt[u]);
-            for (int m = 32; m >= 1; m >>= 1) second = max(second, __shfl_xor(second, m, 64));
-            const int bc = key >> 16;
-            if (t == 0 && bc >= kAnchorMinMatches && bc - second >= kAnchorMinGap) { anchor[(size_t)row * slots + slot] = 128 + bo; s_done = 1; }
-        }
-        __syncthreads();
-        if (s_done) break;
-    }
-}
-
 template <int W, int RPL>
 struct NCfg {
     static constexpr int NV = W * RPL;          // 64-row blocks resident at once
@@ -361,6 +93,15 @@ struct NCfg {
     static constexpr int CAP = 64 * NB;         // ring columns
     static constexpr int THREADS = 64 * W;
 };
+
+// byte address, in plane 0 of the reference ring at `ring`, of the column that the lane of row b0 + lane reads on diagonal k: ((k - b0 - lane) mod CAP) * 16
+template <int CAP>
+__device__ __forceinline__ unsigned ring_byte_addr(int k, int b0, int lane, unsigned ring)
+{
+    int rs = (k - b0 - lane) % CAP;
+    rs += (rs < 0) ? CAP : 0;
+    return (unsigned)rs * 16u + ring;
+}
 
 // P = 6 (nucleotide) or 22 (protein).  MM = column-score mode, host-selected (every mode of an alphabet computes the same sums, see
 // talco_kernel): nucleotide 0 general 5x5, 1 zero N row/column (4x4 core), 2 mode 1 with the match / transition / transversion
@@ -389,11 +130,7 @@ __global__ __launch_bounds__(64 * W, MINW) void talco_lean_kernel(NArgs a)
     // Geometries of three or more blocks per wave (the wide windows) do not keep the first products per row: sixteen registers per block put
     // the 16-wave x 3-block kernel 60 registers over its budget of 128 (212-244 B of scratch per lane, reloaded on the diagonal's critical
     // path: 2.6-3.8 us per diagonal of a 2300-row band).  They form q[m]*M[l][m] again in every cell -- the same first rounding (:386), eight packed multiplies more.
-#if defined(TWL_EXP_QPRE)      // experiment builds: force either form for every geometry
-    constexpr bool QPRE = !(MM == 2) || TWL_EXP_QPRE;
-#else
     constexpr bool QPRE = !((RPL >= 3 || MINW >= 5) && MM == 2);      // (five waves per SIMD: 96 registers)
-#endif
     constexpr int F4 = (P + 2) / 4;                       // float4 per packed column: 2 or 6
     constexpr bool SPARSE = (MM == 3), PRESIM = (MM == 4);
     constexpr int RP = PRESIM ? 1 : F4;                  // ring planes: presim keeps only {X letter, gap, gapOpen, gapExtend}
@@ -429,6 +166,7 @@ __global__ __launch_bounds__(64 * W, MINW) void talco_lean_kernel(NArgs a)
         for (int t = threadIdx.x; t < 21 * 6; t += C::THREADS) s_M4[t] = reinterpret_cast<const float4 *>(a.M24)[t];
     }
 
+    // ---- 1. job setup: the next pair (tile job, scout) off the queue, its lengths, denominator and start cell, the records of earlier tile-parallel launches ----
     int specRound = 0;
     for (;;) {
         int item;
@@ -554,7 +292,7 @@ __global__ __launch_bounds__(64 * W, MINW) void talco_lean_kernel(NArgs a)
         const unsigned long long st_t0 = __builtin_amdgcn_s_memtime();
 #endif
 
-        while (!last_tile) {   // ---- Align_freq tile loop, TALCO-XDrop.cpp:77-106 ----
+        while (!last_tile) {   // ---- 2. tile setup.  Align_freq tile loop, TALCO-XDrop.cpp:77-106: where this tile starts (SPEC: the partner's word; MT 3: a record instead of the tile) ----
 #ifdef TWL_KERNEL_STAMPS
             const unsigned long long st_tile0 = __builtin_amdgcn_s_memtime();
 #endif
@@ -613,7 +351,7 @@ __global__ __launch_bounds__(64 * W, MINW) void talco_lean_kernel(NArgs a)
             // the nucleotide matrix values of mode 2 (match / transition / transversion) in vector registers: see the column score of the geometries that form the first products per cell
             float vmA = a.M[0], vmB = a.M[2], vmC = a.M[1];
             asm volatile("" : "+v"(vmA), "+v"(vmB), "+v"(vmC));
-            // ---- per-slot state ----
+            // ---- 2.1 per-slot state, the loaders of query rows and reference columns ----
             float S1[RPL], I1[RPL], D1[RPL], LS2[RPL];
             int CS1[RPL], CI1[RPL], CD1[RPL], LCS2[RPL];
             float qv[RPL][QN], gopq[RPL], gexq[RPL], qM[RPL][NQM];
@@ -716,11 +454,7 @@ __global__ __launch_bounds__(64 * W, MINW) void talco_lean_kernel(NArgs a)
                     guardBad = guardBad | (__builtin_amdgcn_ballot_w64(bad) != 0ull);
                 }
             };
-            auto ring_addr = [&](int r, int k) __attribute__((always_inline)) {      // ((k - 64*blk - lane) mod CAP) * 16
-                int rs = (k - b0[r] - lane) % CAP;
-                rs += (rs < 0) ? CAP : 0;
-                ra[r] = (unsigned)rs * 16u + lds_off(s_ring);
-            };
+            auto ring_addr = [&](int r, int k) __attribute__((always_inline)) { ra[r] = ring_byte_addr<CAP>(k, b0[r], lane, lds_off(s_ring)); };
 
 #pragma unroll
             for (int r = 0; r < RPL; ++r) {
@@ -743,7 +477,7 @@ __global__ __launch_bounds__(64 * W, MINW) void talco_lean_kernel(NArgs a)
             }
             __syncthreads();
 
-            // ---- Tile, TALCO-XDrop.cpp:233-689 ----
+            // ---- 2.2 Tile, TALCO-XDrop.cpp:233-689: the band bookkeeping ----
             // The band bookkeeping lives twice: as "uniform vectors" (v*: the same value in every lane, in vector registers, so
             // that the per-diagonal arithmetic and every lane test run on the four vector units) and, for the few branches, as the
             // scalars Lk / Uk read back once per diagonal.  Bands: diagonal k as (vL, vU); diagonal k-1 as (vlo1, vw1 = width-1),
@@ -798,6 +532,7 @@ __global__ __launch_bounds__(64 * W, MINW) void talco_lean_kernel(NArgs a)
             // GEN (round 6): true = the general step, which tests for the special diagonals (k == 0, tile 0's first row / column); false = the plain step the
             // loops below switch to once `spec` has gone false for good: the test does not exist in it.  The every-8th-diagonal hook runs at the END of a step,
             // behind the band update (until round 5 in front of the barrier, behind a five-instruction test).
+            // ---- 3. step: one diagonal (and the every-8th-diagonal hook) ----
             auto stop_tile = [&]() __attribute__((always_inline)) { go = false; kStop = (int)0x80000000; };
             auto hook = [&](auto PHtag) __attribute__((always_inline)) {
                 constexpr int PH = decltype(PHtag)::value;
@@ -807,11 +542,7 @@ __global__ __launch_bounds__(64 * W, MINW) void talco_lean_kernel(NArgs a)
 #pragma unroll
                     for (int r = 0; r < RPL; ++r) {
                         const int bb = b0[r];
-#if defined(TWL_TB_ALWAYS)      // experiment builds: every window row stores its word, as until round 4
-                        (void)bb;
-#else
                         if (((tbMust >> r) & 1u) != 0u || (bb + 63 >= tbL0 && bb <= tbU0 + 8))
-#endif
                             *reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(tb) + tbOff + (unsigned)(256 * (r * W + w))) = tbacc[r];
                         tbacc[r] = 0;
                     }
@@ -831,17 +562,6 @@ __global__ __launch_bounds__(64 * W, MINW) void talco_lean_kernel(NArgs a)
                 constexpr bool TB = (PH != 2), CONV = (PH != 0);
                 asm volatile("; TWL_STEP PH=%c0 GEN=%c1 (a comment: tools/isa_block_step.py finds the diagonal loops by it)" ::"n"(PH), "n"((int)GEN));
                 TWL_STAMP(t_head);
-#if defined(TWL_EXP_SALU)      // timing experiment: 24 extra scalar instructions per wave and diagonal
-                { int xs = k; 
-#pragma unroll
-                  for (int t = 0; t < 24; ++t) asm volatile("s_add_u32 %0, %0, 1" : "+s"(xs));
-                  asm volatile("" :: "s"(xs)); }
-#elif defined(TWL_EXP_VALU)    // timing experiment: 24 extra vector instructions per wave and diagonal
-                { int xv = lane;
-#pragma unroll
-                  for (int t = 0; t < 24; ++t) asm volatile("v_add_u32 %0, %0, 1" : "+v"(xv));
-                  asm volatile("" :: "v"(xv)); }
-#endif
                 const unsigned kk16 = (unsigned)(k + 1) << 16;                // tag of this diagonal's row reductions (k + 1 <= 65535)
                 const unsigned vwidth1 = (unsigned)(vU - vL);
                 vcells += vwidth1 + 1u;
@@ -878,7 +598,7 @@ __global__ __launch_bounds__(64 * W, MINW) void talco_lean_kernel(NArgs a)
                         if constexpr (MT == 0 && RPL >= 2) { if (r == 0) TWL_SETPRIO(2); else TWL_SETPRIO(3); }
                         else TWL_SETPRIO(2);
                         const int i = b + lane;
-                        // ---- loads: mailbox of the previous block, reference column of this cell ----
+                        // ---- 3.1 loads: mailbox of the previous block, reference column of this cell ----
                         float eS, eI; int eCS = 0, eCI = 0;
                         if constexpr (CONV) {
                             const nuc_i4 e = lds_ld<nuc_i4>(vprev + exRel[r]);
@@ -894,7 +614,7 @@ __global__ __launch_bounds__(64 * W, MINW) void talco_lean_kernel(NArgs a)
                             const float4 c1 = lds_ld128(ra[r] + CAP * 16);
                             const float rc[5] = {c0.x, c0.y, c0.z, c0.w, c1.x};
                             rg = c1.y; gopr = c1.z; gexr = c1.w;
-                            // ---- column score, :378-395 (order: per l the products summed left to right, accumulated over l) ----
+                            // ---- 3.2 column score, :378-395 (order: per l the products summed left to right, accumulated over l) ----
                             // rows {0,1} and {2,3} side by side: t[l][m] = (q[m]*M[l][m]) * r[l]; s_l = ((t0 + t1) + t2) + t3 (+ t4)
                             constexpr int NM = (MM == 0) ? 5 : (MM == 5 ? 1 : 4);
                             const nuc_f2 r01 = nuc_f2{c0.x, c0.y}, r23 = nuc_f2{c0.z, c0.w};
@@ -903,17 +623,6 @@ __global__ __launch_bounds__(64 * W, MINW) void talco_lean_kernel(NArgs a)
                                 s01 = qP[r][0] * r01; s23 = qP[r][1] * r23;
 #pragma unroll
                                 for (int m = 1; m < NM; ++m) { s01 = s01 + qP[r][2 * m] * r01; s23 = s23 + qP[r][2 * m + 1] * r23; }
-#if defined(TWL_EXP_PACKED_SCORE)      // experiment builds: the packed form of rounds 4-5 (matrix values as scalar operands, v_pk_mul / v_pk_add)
-                            } else if constexpr (true) {
-                                const float mA = a.M[0], mB = a.M[2], mC = a.M[1];
-                                auto fp = [&](int m, int h) __attribute__((always_inline)) {
-                                    const int l0 = 2 * h, l1 = 2 * h + 1;
-                                    return nuc_f2{qv[r][m] * ((l0 == m) ? mA : (((l0 ^ m) == 2) ? mB : mC)), qv[r][m] * ((l1 == m) ? mA : (((l1 ^ m) == 2) ? mB : mC))};
-                                };
-                                s01 = fp(0, 0) * r01; s23 = fp(0, 1) * r23;
-#pragma unroll
-                                for (int m = 1; m < 4; ++m) { s01 = s01 + fp(m, 0) * r01; s23 = s23 + fp(m, 1) * r23; }
-#endif
                             } else {      // the first products of this row formed here (see QPRE): same operations, same order
                                 // Round 6: as plain fp32 operations on VECTOR registers.  Measured (tools/micro/issue_rates5.hip, profiles/r06/issue_rates5.log): an fp32
                                 // add / mul / fma on vector registers issues at 3.6-3.8 per ns and CU, the same multiply with a scalar register as an operand at 2.2 (as
@@ -1021,7 +730,7 @@ __global__ __launch_bounds__(64 * W, MINW) void talco_lean_kernel(NArgs a)
                         if constexpr (DUMP) {      // diagnostics build of the same code: the score of every cell the band visits
                             if (inband) a.simdump[(size_t)(qry_idx + i) * (size_t)R + (size_t)(ref_idx + k - i)] = sim;
                         }
-                        // ---- neighbours ----
+                        // ---- 3.3 neighbours ----
                         const float LS1 = dpp_shr1_f(eS, S1[r]);
                         const float LI1 = dpp_shr1_f(eI, I1[r]);
                         int LCS1 = 0, LCI1 = 0;
@@ -1030,7 +739,7 @@ __global__ __launch_bounds__(64 * W, MINW) void talco_lean_kernel(NArgs a)
                         const bool up_ok = t1 <= vw1;                      // i   in band(k-1)
                         const bool left_ok = (t1 - 1u) <= vw1;             // i-1 in band(k-1)
                         const bool diag_ok = (unsigned)(i - vlo2p) <= vw2; // i-1 in band(k-2)
-                        // ---- recurrence, :445-497 ----
+                        // ---- 3.3 recurrence, :445-497 ----
                         float match = diag_ok ? LS2[r] + sim : -inf;
                         if (__builtin_expect(special, 0)) {
                             const int j = k - i;
@@ -1057,6 +766,7 @@ __global__ __launch_bounds__(64 * W, MINW) void talco_lean_kernel(NArgs a)
                         float Sv = isM ? match : Gv;
                         Sv = (Sv < thr) ? -inf : Sv;                                               // :495-497
 
+                        // ---- 3.4 pointers: convergence pointers (:520-547) here, the traceback nibble (:548-557) behind the reductions ----
                         if constexpr (CONV) {                                                      // :520-547
                             int CSn, CIn, CDn;
                             const int i16 = i & 0xFFFF;
@@ -1080,7 +790,7 @@ __global__ __launch_bounds__(64 * W, MINW) void talco_lean_kernel(NArgs a)
                                 asm volatile("ds_max_u64 %0, %1" ::"v"(lds_off(&s_team[(k == marker) ? 3 : 2])), "v"(key) : "memory");
                             }
                         }
-                        // ---- reductions of this diagonal (:501-503, :563-583), all lanes issuing, see vTrash ----
+                        // ---- 3.5 reductions of this diagonal (:501-503, :563-583), all lanes issuing, see vTrash ----
                         const float Sin = inband ? Sv : -inf;             // out-of-band lanes take no part
                         lds_max_f32_off<O_RED>((Sin > msp) ? vcur : vTrashRed, Sin);
                         const unsigned long long vm = __builtin_amdgcn_ballot_w64(Sin > -inf);
@@ -1126,7 +836,7 @@ __global__ __launch_bounds__(64 * W, MINW) void talco_lean_kernel(NArgs a)
                 }
                 TWL_STAMP(t_bar);
 
-                // ---- post: the band of the next diagonal, :563-604 ----
+                // ---- 3.6 post: the band of the next diagonal, :563-604 ----
                 // {running max, low-end tag, high-end tag}: a tag from an older diagonal is smaller than this diagonal's, so when no
                 // row survived the differences below come out as newU <= -1 and newL >= 65536: an empty band, caught by the next test
                 const nuc_i4 rd = lds_ld<nuc_i4>(vcur + O_RED);
@@ -1238,6 +948,7 @@ __global__ __launch_bounds__(64 * W, MINW) void talco_lean_kernel(NArgs a)
                 }
             };
 
+            // ---- 4. phase driver: phases A, B, C of the tile on the step above; SPEC: polls and settles with the partner; MT 2: the scout's end ----
             if (steps_left < 0) { tile_err = 3; go = false; }
 #ifdef TWL_KERNEL_STAMPS
             st_setup += __builtin_amdgcn_s_memtime() - st_tile0;
@@ -1366,7 +1077,7 @@ __global__ __launch_bounds__(64 * W, MINW) void talco_lean_kernel(NArgs a)
                     *reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(tb) + tbOff + (unsigned)(256 * (r * W + w))) = tbacc[r];
             }
 
-            // ---- tile exit, :615-682 ----
+            // ---- 5. tile exit, :615-682 ----
             // after the loop (lo1, w1) is the band of diagonal last_k (rotated once more at its end)
             int conv_q = 0, conv_r = 0, tb_state = 0, start_k = 0;
             bool bad = false;
@@ -1418,7 +1129,7 @@ __global__ __launch_bounds__(64 * W, MINW) void talco_lean_kernel(NArgs a)
                     }
                 }
                 int n = 0;
-                {   // Traceback, :134-231, addressed by (diagonal, row) instead of a ragged offset.  One lane walks the pointers; a walk
+                {   // ---- 6. walk ----  Traceback, :134-231, addressed by (diagonal, row) instead of a ragged offset.  One lane walks the pointers; a walk
                     // straight out of HBM costs a dependent L2 round trip per step, so the wave fetches the pointer words in patches of
                     // 64 rows x 16 groups of 8 diagonals (a path of matches crosses exactly that) into the reference ring, which is dead
                     // until the next tile, and the walk reads LDS.
@@ -1533,6 +1244,7 @@ __global__ __launch_bounds__(64 * W, MINW) void talco_lean_kernel(NArgs a)
             }      // (tile not thrown away)
             }      // (tile started)
         }
+        // ---- 7. job end: the pair's verdict, length and band cells; the records and counters of the tile-parallel launches ----
         if constexpr (SPEC) {
             if (err != 0 && (!teamExit || timedOut)) {       // this workgroup fails the pair: tell the partner (it may be waiting for a start)
                 iEnded = true;

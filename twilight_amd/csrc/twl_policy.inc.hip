@@ -15,7 +15,7 @@ struct Knobs {
     int mt_max_pairs, mt_min_marker, mt_tail_pct, mt_wide, assume_onehot_query, no_spec, thr_small; ProtMode prot_mode; int prot_corridor;
     int mt_thr_jobs, mt_rounds, mt_anchor, mt_lead, mt_marg, mt_marg_lat, mt_lead2, mt_lead2_lat;      // of a tile-parallel level (plan_tile_level)
 };
-// fast_div's guard (talco_nuc.hip.h): non-zero scores within [2^-10, 2^10]; anything else takes the IEEE-division kernel
+// fast_div's guard (talco_div.hip.h): non-zero scores within [2^-10, 2^10]; anything else takes the IEEE-division kernel
 inline bool fast_div_in_range(const float *M, int n, float gap_char)
 {
     auto inRange = [](float x) { const float ax = std::fabs(x); return x == 0.0f || (ax >= 0.0009765625f && ax <= 1024.0f); };
@@ -217,7 +217,7 @@ struct TileFacts {
     bool can_small = false;               // the instantiation has the 512-row throughput geometry (nucleotide, 4-wave throughput geometry, not wide) ...
     bool small_tiles = false;             // ... and the earlier levels of this pass fitted it
     int n_run = 0, marker = 0, seq_len = 0;
-    int rec_words = 0;                    // words of a tile's record (talco_nuc.hip.h, kMtRec)
+    int rec_words = 0;                    // words of a tile's record (talco_mt.hip.h, kMtRec)
     const int32_t *order = nullptr;       // the pairs that run
     const int32_t *h_len = nullptr;       // [pair][2]
 };
@@ -261,7 +261,7 @@ TilePlan plan_tile_level(const TileFacts &f, const Knobs &k, std::vector<int32_t
     pl.spath_ints = np * (size_t)pl.sp_pitch;
     pl.stat_bytes = 4 * sizeof(unsigned long long) + np * 8 * sizeof(int32_t);      // counters, then the per-pair frontier
     pl.jobs_ints = jobs.size();
-    // scouts of the narrow geometries start from an anchored cell where the profiles give one (talco_nuc.hip.h, mt_anchor_kernel)
+    // scouts of the narrow geometries start from an anchored cell where the profiles give one (talco_mt.hip.h, mt_anchor_kernel)
     pl.anchors = !f.wide && k.mt_anchor && pl.nScout > 0;
     pl.anchor_ints = pl.anchors ? np * pl.slots : 0;
     pl.thr = !f.wide && pl.nTile > k.mt_thr_jobs;

@@ -24,6 +24,7 @@ struct RunCtx {
     LevelTotals totals;
     std::vector<LevelRecord> levels;
     Shard shard;
+    std::function<void(twl_store *)> onStoreCreated;      // createStore calls it once per replica, behind the upload and ahead of the first level, then forgets it (place_tree.cpp squeezes the backbone's groups there)
     struct Raw { char *p = nullptr; size_t cap = 0; bool pinned = false; char *get(size_t n); ~Raw(); Raw() = default; Raw(Raw &&o) noexcept : p(o.p), cap(o.cap), pinned(o.pinned) { o.p = nullptr; o.cap = 0; } Raw(const Raw &) = delete; };      // grow-only, never zero-filled host buffer
     ~RunCtx();
 };

@@ -71,6 +71,11 @@ void createStore(RunCtx &ctx, SequenceDB *db, Option *option)
     for (auto &t : th) t.join();
     for (auto &r : res)
         if (r.first != TWL_OK) { std::cerr << "ERROR: twl_store_create failed (" << r.first << "): " << r.second << '\n'; exit(1); }
+    if (ctx.onStoreCreated) {
+        const std::function<void(twl_store *)> hook = std::move(ctx.onStoreCreated);
+        ctx.onStoreCreated = nullptr;
+        for (twl_store *st : ctx.stores) hook(st);
+    }
 }
 
 // Runs fn(replica index) for every replica on its own host thread; stops the run on the first library error.

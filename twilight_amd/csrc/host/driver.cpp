@@ -74,6 +74,7 @@ bool parseCommandLine(int argc, char **argv, Option &o, bool allowPlacement, boo
         else if (flag(a, nullptr, "--test-no-ownership")) o.testNoOwnership = true;
         else if (flag(a, nullptr, "--test-fork-host-staged")) o.testForkHostStaged = true;
         else if (allowPlacement && flag(a, "-a", "--alignment")) o.backboneAlnFile = val();
+        else if (allowPlacement && flag(a, nullptr, "--place-on-tree")) o.placeOnTree = true;
         else if (allowPlacement && flag(a, nullptr, "--test-place-chunk")) o.testPlaceChunk = std::max(0, atoi(val()));
         else if (allowMerge && flag(a, "-f", "--files")) o.msaDir = val();
         else if (allowSubtrees && flag(a, "-m", "--max-subtree")) {
@@ -118,6 +119,13 @@ bool parseCommandLine(int argc, char **argv, Option &o, bool allowPlacement, boo
         if (o.hostStaged) { std::cerr << "ERROR: --host-staged is not available with --iterations.\n"; exit(1); }
         if (o.gpuIdx.size() > 1 || o.gpuNum > 1) { std::cerr << "ERROR: --iterations runs on one GPU: give at most one --gpu-index.\n"; exit(1); }
     }
+    if (o.placeOnTree) {                   // placement along a tree (place_tree.cpp): -a, -t, -i, -o on one GPU, rows device-resident
+        if (o.backboneAlnFile.empty() || o.treeFile.empty()) { std::cerr << "ERROR: --place-on-tree needs both -a (the backbone alignment) and -t (a tree over its rows and the new sequences).\n"; exit(1); }
+        if (subtreesGiven || !o.msaDir.empty()) { std::cerr << "ERROR: --place-on-tree cannot be combined with -m or -f.\n"; exit(1); }
+        if (o.hostStaged) { std::cerr << "ERROR: --host-staged is not available with --place-on-tree.\n"; exit(1); }
+        if (o.gpuIdx.size() > 1 || o.gpuNum > 1) { std::cerr << "ERROR: --place-on-tree runs on one GPU: give at most one --gpu-index.\n"; exit(1); }
+        if (!o.writeTreeFile.empty() || o.treeSeeds > 0) { std::cerr << "ERROR: --place-on-tree cannot be combined with --write-tree or --tree-seeds: the tree is given with -t.\n"; exit(1); }
+    }
     if (subtreesGiven) {                   // subtrees (subtrees.cpp): the tree+sequences mode only, on one GPU, rows device-resident
         if (!o.msaDir.empty() || !o.backboneAlnFile.empty()) { std::cerr << "ERROR: -m (alignment in subtrees) cannot be combined with -a or -f.\n"; exit(1); }
         if (o.hostStaged) { std::cerr << "ERROR: --host-staged is not available with -m (alignment in subtrees).\n"; exit(1); }
@@ -129,8 +137,14 @@ bool parseCommandLine(int argc, char **argv, Option &o, bool allowPlacement, boo
         if (o.hostStaged) { std::cerr << "ERROR: --host-staged is not available in merge mode (-f).\n"; exit(1); }
         if (o.gpuIdx.size() > 1 || o.gpuNum > 1) { std::cerr << "ERROR: merge mode (-f) runs on one GPU: give at most one --gpu-index.\n"; exit(1); }
         o.alnMode = MERGE_MSA;
+    } else if (o.placeOnTree) {                   // placement along a tree (reference option.cpp: -t -a -i -o); its refusals are above
+        if (o.seqFile.empty() || o.outFile.empty()) return false;
+        o.alnMode = PLACE_W_TREE;
     } else if (!o.backboneAlnFile.empty()) {      // placement (reference option.cpp:15-22): -a -i -o without -t
-        if (!o.treeFile.empty()) { std::cerr << "ERROR: -a together with -t (placement with a tree) is not supported yet.\n"; exit(1); }
+        if (!o.treeFile.empty()) {
+            std::cerr << "ERROR: -a together with -t (placement with a tree) is not supported yet without --place-on-tree: it re-aligns the backbone's groups along the tree.\n";
+            exit(1);
+        }
         if (o.seqFile.empty() || o.outFile.empty()) return false;
         if (o.hostStaged) { std::cerr << "ERROR: --host-staged is not available in placement mode (-a).\n"; exit(1); }
         if (o.gpuIdx.size() > 1 || o.gpuNum > 1) { std::cerr << "ERROR: placement mode (-a) runs on one GPU: give at most one --gpu-index.\n"; exit(1); }

@@ -301,7 +301,9 @@ void Tree::convert2binaryTree()            // tree.cpp:528-586
 }
 
 // tree.cpp:588-696: move the root to the middle of the tree's diameter (in edges) so that sibling levels are wide
-void Tree::reroot()
+// placement (PLACE_W_TREE, tree.cpp:596-600 and :627-629): the search starts at the first placed leaf and only placed nodes count as farthest,
+// so the root moves to the middle of the longest path between two placed nodes
+void Tree::reroot(bool placement)
 {
     int depth0 = 0, depth1 = 0, depth2 = 0;
     for (auto &kv : allNodes) depth0 = std::max<int>(depth0, (int)kv.second->level);
@@ -309,7 +311,7 @@ void Tree::reroot()
     for (auto &kv : allNodes) depth1 = std::max<int>(depth1, (int)kv.second->level);
     Node *start = nullptr;
     for (auto &kv : allNodes)
-        if (kv.second->is_leaf()) { start = kv.second; break; }
+        if (kv.second->is_leaf() && (!placement || kv.second->placed)) { start = kv.second; break; }
 
     auto farthestFrom = [&](Node *from, std::unordered_map<Node *, Node *> &cameFrom) {
         std::queue<Node *> q;
@@ -329,7 +331,7 @@ void Tree::reroot()
                 dist[v] = dist[u] + 1;
                 cameFrom[v] = u;
                 q.push(v);
-                if (dist[v] > dist[far]) far = v;
+                if (dist[v] > dist[far] && (!placement || v->placed)) far = v;
             }
         }
         return far;
@@ -342,6 +344,9 @@ void Tree::reroot()
     std::reverse(path.begin(), path.end());
     Node *newRoot = path[path.size() / 2];
     if (newRoot->identifier == root->identifier) return;      // note: leaves numLeaves/weights/m_numLeaves untouched (:658)
+    // one placed leaf: the path is that leaf alone.  The reference moves the root INTO the leaf, which then trades names with the old root and
+    // is a leaf no more, so that getPlacementTree finds no placed leaf at all; here the tree keeps its root (a deliberate difference).
+    if (placement && newRoot->is_leaf()) return;
 
     // Turn the path new root -> old root upside down, walking it from the bottom: every edge keeps its length and its two ends trade places,
     // so a node of the path hangs under the neighbour we came from, carries the length of the edge between them, loses that neighbour as a

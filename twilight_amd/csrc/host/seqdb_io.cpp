@@ -392,6 +392,8 @@ void readSequences(const std::string &fileName, SequenceDB *database, Option *op
     gzbuffer(f, 1 << 22);
     ChunkReader in(f);
     const int seqNum_init = (int)database->sequences.size();
+    // placement along a tree reads two files into one database: the backbone's rows first, then the new sequences, which become the placed leaves (io.cpp:58)
+    const bool onTree = option->alnMode == PLACE_W_TREE, placed = onTree && fileName == option->seqFile;
     int seqNum = seqNum_init, maxLen = 0, minLen = INT_MAX;
     uint64_t totalLen = 0;
     std::vector<int> lens;
@@ -409,7 +411,7 @@ void readSequences(const std::string &fileName, SequenceDB *database, Option *op
         totalLen += L;
         Node *leaf = tree->allNodes[name];
         database->addSequence(seqNum, name, seq, leaf->grpID, leaf->weight, option->debug);
-        leaf->placed = false;
+        leaf->placed = placed;
         ++seqNum;
         lens.push_back(L);
     }
@@ -424,6 +426,10 @@ void readSequences(const std::string &fileName, SequenceDB *database, Option *op
         for (auto &kv : database->name_map) names.insert(kv.first);
         phylogeny::pruneTree(tree, names);
     }
+    if (seqNum == seqNum_init && onTree) {
+        std::cerr << (placed ? "ERROR: no new sequence of " : "ERROR: no backbone row of ") << fileName << " is a leaf of the tree.\n";
+        exit(1);
+    }
     if (seqNum == seqNum_init) { std::cerr << "Error: no sequences were read from the input.\n"; exit(1); }
 
     std::sort(lens.begin(), lens.end());
@@ -431,12 +437,17 @@ void readSequences(const std::string &fileName, SequenceDB *database, Option *op
     const uint32_t medLen = lens[(seqNum - seqNum_init) / 2];
     const int minTh = (option->lenDev > 0) ? (int)(medLen * (1 - option->lenDev)) : option->minLen;
     const int maxTh = (option->lenDev > 0) ? (int)(medLen * (1 + option->lenDev)) : option->maxLen;
+    if (onTree && !placed) {                  // the backbone: no flags (io.cpp:137), its own summary (:191-196)
+        std::cerr << "==== Backbone Alignment ====\nNumber : " << (seqNum - seqNum_init) << "\nLength:  " << avgLen << '\n';
+        return;
+    }
     std::atomic<int> numLowQ{0};
     uint8_t isAmbig[256];                     // letterIdx(type, toupper(c)) == N / X, tabulated once
     for (int c = 0; c < 256; ++c) isAmbig[c] = (letterIdx(option->type, (char)toupper(c)) == ((option->type == 'n') ? 4 : 20)) ? 1 : 0;
 #pragma omp parallel for schedule(static)
     for (int i = 0; i < seqNum; ++i) {                                                  // io.cpp:134-162
         auto *s = database->sequences[i];
+        if (onTree && i < seqNum_init) continue;                                        // (:141: a backbone row is no placed leaf)
         s->lowQuality = (s->len > maxTh || s->len < minTh);
         if (!s->lowQuality) {
             int cnt = 0;

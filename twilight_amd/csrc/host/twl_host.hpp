@@ -64,7 +64,7 @@ struct Tree {
     void calLeafNum();
     void calSeqWeight();
     void parseNewick(std::string &newick);
-    void reroot();
+    void reroot(bool placement = false);      // placement: between placed nodes only (PLACE_W_TREE, after both reads)
     void convert2binaryTree();
     Tree *prune(std::unordered_set<std::string> &seqs);
 
@@ -141,7 +141,8 @@ struct Option {
     bool testNoOwnership = false; // --test-no-ownership: a sharded run deals and exchanges every level (no subtree ownership below a cut)
     int testVirtualDevices = 0;  // --test-virtual-devices n: n replicas of the store on the first device (the several-replica path of the resident kernel on a one-GPU box)
     bool hostStaged = false;     // --host-staged: build profiles on the host and stage them per level (default: device-resident rows)
-    std::string backboneAlnFile; // -a / --alignment: the existing alignment new sequences are placed into (alnMode PLACE_WO_TREE)
+    std::string backboneAlnFile; // -a / --alignment: the existing alignment new sequences are placed into (alnMode PLACE_WO_TREE; with -t and --place-on-tree PLACE_W_TREE)
+    bool placeOnTree = false;    // --place-on-tree: -a together with -t places the new sequences along the tree (place_tree.cpp)
     int testPlaceChunk = 0;      // --test-place-chunk n: placement aligns at most n sequences per level (default: sized to device memory)
     std::string msaDir;          // -f / --files: a directory of alignments to merge into one (alnMode MERGE_MSA)
     bool typeGiven = false;      // --type was given (a merge detects the type from its first file otherwise)
@@ -328,6 +329,7 @@ void downloadRows(SequenceDB *database, Tree *T);
 int runDefaultAlignment(Option &option, alnFunction kernel, alnFunction deferredKernel, bool writeOutput = true,
                         const std::function<void(SequenceDB *)> &atEnd = nullptr, const std::function<void(SequenceDB *)> &beforeAlign = nullptr);
 // allowPlacement: the binary carries the placement mode (twilight-mi355x): -a/--alignment with -i/-o and no -t selects PLACE_WO_TREE
+//                 ... and -a with -t, -i, -o and --place-on-tree selects PLACE_W_TREE (without the flag -a with -t is refused)
 // allowMerge: the binary carries the merge mode as well: -f/--files with -o and none of -t, -i, -a selects MERGE_MSA
 // allowSubtrees: the binary carries the subtree mode too: -m/--max-subtree N with -t, -i, -o sets Option::maxSubtree
 // allowGuide: the binary builds the guide tree itself when none is given: -i and -o without -t, -a or -f sets Option::buildTree
@@ -348,6 +350,14 @@ int runIterations(Option &option);
 // PLACE_WO_TREE (place.cpp, libtwl_host.so): the sequences of option.seqFile placed into the alignment option.backboneAlnFile, written to
 // option.outFile.  Returns the final alignment length.
 int runPlacement(Option &option);
+// PLACE_W_TREE (place_tree.cpp, libtwl_host.so): the sequences of option.seqFile placed into the alignment option.backboneAlnFile where the tree
+// option.treeFile says they belong, written to option.outFile.  Returns the final alignment length.
+int runPlacementOnTree(Option &option);
+// The host half of that mode up to the level schedule (place_tree.cpp; tests/place_tree_dump.cpp prints it): both reads, the reroot between placed
+// nodes, the placed marks and the backbone group of every placed node.  subT: the whole tree's copy; returns the tree of the placed nodes
+// (getPlacementTree, sequencedb.cpp:148-246, without its host loop over the all-gap columns: the groups still have the backbone's width).
+struct PlacementGroups { std::vector<Node *> nodes; int32_t backboneLen = 0, backboneRows = 0; };      // nodes: the placement tree's inner nodes that bring members, by name
+Tree *readPlacementInputs(Option &option, SequenceDB &database, Tree *subT, PlacementGroups &groups);
 // MERGE_MSA (merge.cpp, libtwl_host.so): the alignments found under option.msaDir merged into one, written to option.outFile.  Returns the
 // final alignment length.
 int runMerge(Option &option);

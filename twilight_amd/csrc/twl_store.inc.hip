@@ -243,6 +243,7 @@ struct twl_store {
     Buf d_gather;                // rows packed back to back, on their way to or from the host
     Buf x_send, x_recv;          // device blocks of the subtree exchange of a sharded run (twl_store_exchange_buffers)
     double prepare_ms = 0, commit_ms = 0;
+    double squeeze_ms = 0;       // HIP-event time of the kernels of the last twl_store_squeeze_groups (twl_backbone.inc.hip)
 };
 
 namespace {

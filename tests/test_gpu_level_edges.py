@@ -163,12 +163,14 @@ def test_write_back_of_caller_built_paths(gpu, level):
     st.close()
 
 
-def _restore_level(twl, seq_type, cases, specs, thr=0.95, out_stride=None, select=None):
+def _restore_level(twl, seq_type, cases, specs, thr=0.95, out_stride=None, select=None, store_all=False, keep=None):
     """prepare -> align_in_hbm -> restore -> read_final -> (write_final for handed-back pairs) -> commit_from_dp(restored=...), every step
-    against the checker.  specs[i] is None for an ordinary pair: it must not be handed back."""
+    against the checker.  specs[i] is None for an ordinary pair: it must not be handed back.  keep: a dict that receives what the run left
+    (rows, the DP lengths, the committed lengths and, with store_all, the cached profile under every reference side's id) for tests that
+    hold another flow to this one (tests/test_gpu_level_exchange.py)."""
     from twilight_amd import level as L
 
-    seqs, pairs, ids = _level(cases)
+    seqs, pairs, ids = _level(cases, store_all=store_all)
     p = twl.make_params(LC.matrix_of(seq_type))
     st = L.Store(seqs, seq_type)
     lens, info = st.prepare(p, pairs, gappy_threshold=thr)
@@ -210,6 +212,8 @@ def _restore_level(twl, seq_type, cases, specs, thr=0.95, out_stride=None, selec
             continue
         for sid, w in zip(flat, want):
             assert rows[sid] == w, f"pair {i}: row {sid} after write-back"
+    if keep is not None:
+        keep.update(rows=rows, dp_len=[int(x) for x in n], plen=list(plen), caches=[st.cache(2 * i) for i in range(len(cases))] if store_all else None)
     st.close()
     return sel, fin
 

@@ -168,6 +168,25 @@ def set_knob(key: int, value: int):
     _check(load_library().twl_set_knob(C.c_int(key), C.c_int(value)))
 
 
+def copy_to_device(dst_dev: int, data: bytes, device=0):
+    """twl_copy_to_device: `data` to the device address dst_dev (an integer, e.g. a buffer of level.Store.exchange_buffers)."""
+    _check(load_library().twl_copy_to_device(C.c_int(device), C.c_void_p(dst_dev), data, C.c_uint64(len(data))))
+
+
+def copy_from_device(src_dev: int, n_bytes: int, device=0) -> bytes:
+    """twl_copy_from_device: n_bytes from the device address src_dev."""
+    buf = C.create_string_buffer(max(1, n_bytes))
+    _check(load_library().twl_copy_from_device(C.c_int(device), buf, C.c_void_p(src_dev), C.c_uint64(n_bytes)))
+    return buf.raw[:n_bytes]
+
+
+def copy_rows_from_device(src_dev: int, src_pitch: int, width: int, rows: int, device=0) -> bytes:
+    """twl_copy_rows_from_device: the first `width` bytes of `rows` rows that lie src_pitch bytes apart from src_dev on, back to back."""
+    buf = C.create_string_buffer(max(1, width * rows))
+    _check(load_library().twl_copy_rows_from_device(C.c_int(device), buf, C.c_uint64(width), C.c_void_p(src_dev), C.c_uint64(src_pitch), C.c_uint64(width), C.c_uint64(rows)))
+    return buf.raw[: width * rows]
+
+
 def plan_describe(params, lens, num_cu=256, qry_onehot=False, wide_streak=0, small_state=0) -> str:
     """twl_plan_describe: the first launch of a nucleotide or protein call in words (no device needed)."""
     wide_streak = int(wide_streak) + (100000 * (32 + int(small_state)) if small_state else 0)      # (1 / -1: the earlier levels of the pass fitted / outgrew the 512-row throughput window)

@@ -372,6 +372,11 @@ int level_rows_block(twl_store *s, bool toBlock, int32_t n_sel, const int32_t *p
     DEVICE_CALL(call, s->d);
     hipStream_t st = call.st;
     LevelBufs *lv = s->lv;
+    // a block inside the level's own exchange buffers has a known end; the whole selection is judged before the first launch
+    int64_t room = -1;
+    for (const Buf *b : {&lv->x_send, &lv->x_recv})
+        if (b->p && (const char *)blk_dev >= (const char *)b->p && (const char *)blk_dev < (const char *)b->p + b->cap) room = (int64_t)((const char *)b->p + b->cap - (const char *)blk_dev);
+    if (const char *why = check_block_rows(toBlock, n_sel, pairs, lens, where, blk_off, s->n_pairs, s->seq_len, s->staged_stride, lv->d_aln.p != nullptr, room)) { g_err = why; return TWL_ERR_BAD_ARGUMENT; }
     const size_t sl2 = 2 * (size_t)s->seq_len, ps = (size_t)s->staged_stride;
     for (int which = 1; which <= 2; ++which) {
         std::vector<int64_t> ro, bo;
@@ -379,7 +384,6 @@ int level_rows_block(twl_store *s, bool toBlock, int32_t n_sel, const int32_t *p
         for (int32_t t = 0; t < n_sel; ++t) {
             const int w = where ? where[t] : 2;
             if (w != which || lens[t] <= 0) continue;
-            if (pairs[t] < 0 || pairs[t] >= s->n_pairs || (size_t)lens[t] > (which == 1 ? sl2 : ps) || (which == 1 && !toBlock)) { g_err = "bad row selection"; return TWL_ERR_BAD_ARGUMENT; }
             ro.push_back((int64_t)pairs[t] * (int64_t)(which == 1 ? sl2 : ps)); bo.push_back(blk_off[t]); ln.push_back(lens[t]);
         }
         if (ro.empty()) continue;

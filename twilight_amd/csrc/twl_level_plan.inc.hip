@@ -134,7 +134,25 @@ inline const char *check_commit(int32_t n, int32_t seq_len, int32_t staged, bool
     return nullptr;
 }
 
-constexpr int kRowGroup = 64;       // members per workgroup of the row rewrite (its scan of the path chunk is shared by them)
+// Everything twl_level_paths_to_block / twl_level_paths_from_block reject in their row selection, decided before the first launch (a refused call
+// has written nothing): the message, or nullptr.  where == nullptr: every row is a row of the path buffer (2).  staged, haveDp as in check_commit.
+// room >= 0: the block starts inside one of the level's own exchange buffers with `room` bytes left from there on, and no row may leave them;
+// room < 0: the block is the caller's memory, its size is not known here.  Rows of length <= 0 are not moved and not looked at.
+inline const char *check_block_rows(bool toBlock, int32_t n_sel, const int32_t *pairs, const int32_t *lens, const uint8_t *where, const int64_t *blk_off,
+                                    int32_t n_pairs, int32_t seq_len, int32_t staged, bool haveDp, int64_t room)
+{
+    for (int32_t t = 0; t < n_sel; ++t) {
+        if (lens[t] <= 0) continue;
+        const int w = where ? where[t] : 2;
+        if (w != 1 && w != 2) return "bad row selection";
+        if (w == 1 && (!toBlock || !haveDp)) return "bad row selection";      // (the DP output is only ever a source)
+        if (pairs[t] < 0 || pairs[t] >= n_pairs || (int64_t)lens[t] > (w == 1 ? 2 * (int64_t)seq_len : (int64_t)staged)) return "bad row selection";
+        if (room >= 0 && (blk_off[t] < 0 || blk_off[t] > room || (int64_t)lens[t] > room - blk_off[t])) return "bad row selection";
+    }
+    return nullptr;
+}
+
+constexpr int kRowGroup = 64;      // members per workgroup of the row rewrite (its scan of the path chunk is shared by them)
 
 struct CommitPlan {                 // (kept by the store for its capacity)
     int32_t maxPath = 0, nChunks = 0;

@@ -232,6 +232,34 @@ class Store:
         p = np.ascontiguousarray(path, dtype=np.int8)
         api._check(_lib().twl_level_write_final(self._h, C.c_int32(pair), p.ctypes.data_as(C.POINTER(C.c_int8)), C.c_int32(len(p))))
 
+    def exchange_buffers(self, send_bytes: int, recv_bytes: int):
+        """twl_level_exchange_buffers: (send, recv), two device buffers of the prepared level as integer addresses (grow-only, owned by the level)."""
+        send, recv = C.c_void_p(), C.c_void_p()
+        api._check(_lib().twl_level_exchange_buffers(self._h, C.c_int64(send_bytes), C.c_int64(recv_bytes), C.byref(send), C.byref(recv)))
+        return int(send.value or 0), int(recv.value or 0)
+
+    @staticmethod
+    def _row_tables(pairs, lens, offsets):
+        if pairs is None:
+            return None, None, None, ()
+        keep = (np.asarray(list(pairs), dtype=np.int32), np.asarray(list(lens), dtype=np.int32), np.asarray(list(offsets), dtype=np.int64))
+        assert len(keep[0]) == len(keep[1]) == len(keep[2])
+        return keep[0].ctypes.data_as(C.POINTER(C.c_int32)), keep[1].ctypes.data_as(C.POINTER(C.c_int32)), keep[2].ctypes.data_as(C.POINTER(C.c_int64)), keep
+
+    def paths_to_block(self, pairs, lens, where, blk_ptr: int, offsets, n_sel: Optional[int] = None):
+        """twl_level_paths_to_block: lens[t] bytes of pair pairs[t]'s row (where[t] == 1: as the DP left it, 2: of the path buffer) to blk_ptr + offsets[t].
+        pairs None sends null tables; n_sel defaults to len(pairs)."""
+        pp, lp, op, keep = self._row_tables(pairs, lens, offsets)
+        w = None if where is None else np.asarray(list(where), dtype=np.uint8)
+        n = len(keep[0]) if n_sel is None and keep else int(n_sel or 0)
+        api._check(_lib().twl_level_paths_to_block(self._h, C.c_int32(n), pp, lp, None if w is None else w.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_void_p(blk_ptr), op))
+
+    def paths_from_block(self, pairs, lens, blk_ptr: int, offsets, n_sel: Optional[int] = None):
+        """twl_level_paths_from_block: lens[t] bytes at blk_ptr + offsets[t] into the path-buffer row of pair pairs[t]."""
+        pp, lp, op, keep = self._row_tables(pairs, lens, offsets)
+        n = len(keep[0]) if n_sel is None and keep else int(n_sel or 0)
+        api._check(_lib().twl_level_paths_from_block(self._h, C.c_int32(n), pp, lp, C.c_void_p(blk_ptr), op))
+
     def commit_from_dp(self, paths: Sequence[Optional[np.ndarray]], path_len: Sequence[int], stride: Optional[int] = None, restored: Sequence[int] = ()):
         """twl_level_commit_from_dp: paths[i] is None -> pair i's path is in HBM already (the DP output, or what twl_level_restore made of it), path_len[i] long."""
         n = self._n_pairs

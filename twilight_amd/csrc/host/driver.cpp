@@ -108,11 +108,19 @@ bool parseCommandLine(int argc, char **argv, Option &o, bool allowPlacement, boo
             o.maskGappy = t;
             maskGiven = true;
         }
+        else if (allowGuide && flag(a, nullptr, "--retree-seeds")) {
+            const char *v = val();
+            char *end = nullptr;
+            const long n = strtol(v, &end, 10);
+            if (end == v || *end != '\0' || n < 2 || n > 16384) { std::cerr << "ERROR: --retree-seeds needs a number of seeds from 2 to 16384 (got " << v << ").\n"; exit(1); }
+            o.retreeSeeds = (int)n;
+        }
         else if (flag(a, nullptr, "--overwrite")) {}
         else if (flag(a, "-h", "--help")) return false;
         else { std::cerr << "ERROR: unsupported option " << a << " (this build covers the tree+sequences alignment mode only)\n"; exit(1); }
     }
     if (maskGiven && o.iterations < 2) { std::cerr << "ERROR: --mask-gappy applies to the trees that --iterations 2 or more rebuilds from an alignment.\n"; exit(1); }
+    if (o.retreeSeeds > 0 && o.iterations < 2) { std::cerr << "ERROR: --retree-seeds applies to the trees that --iterations 2 or more rebuilds from an alignment.\n"; exit(1); }
     if (o.iterations > 1) {                // iterations (retree.cpp): the tree+sequences run or the run that builds its tree, repeated on one GPU, rows device-resident
         if (!o.backboneAlnFile.empty() || !o.msaDir.empty() || subtreesGiven) { std::cerr << "ERROR: --iterations cannot be combined with -a, -f or -m.\n"; exit(1); }
         if (!o.noFilter) { std::cerr << "ERROR: --iterations cannot be combined with --filter: the rebuilt tree would lack the excluded sequences.\n"; exit(1); }

@@ -5,7 +5,7 @@
 //   twilight-mi355x -f DIR -o out.aln [...]                      (built with TWL_MERGE: the alignments of a directory merged, merge.cpp)
 //   twilight-mi355x -t tree.nwk -i seqs.fa -o out.aln -m N [...] (built with TWL_SUBTREE: the tree aligned in subtrees of at most N leaves, subtrees.cpp)
 //   twilight-mi355x -i seqs.fa -o out.aln [--write-tree t.nwk] [--tree-seeds S]   (built with TWL_GUIDE: no tree given, the guide tree is built from the sequences, guide.cpp)
-//   twilight-mi355x [-t tree.nwk] -i seqs.fa -o out.aln --iterations K [--mask-gappy T]   (TWL_GUIDE: the run K times, the tree rebuilt from every alignment but the last, retree.cpp)
+//   twilight-mi355x [-t tree.nwk] -i seqs.fa -o out.aln --iterations K [--mask-gappy T] [--retree-seeds S]   (TWL_GUIDE: the run K times, the tree rebuilt from every alignment but the last, retree.cpp)
 #include "twl_host.hpp"
 
 #include "../../../include/twl_align.h"
@@ -87,9 +87,10 @@ int main(int argc, char **argv)
         if (guide) std::cerr << "       twilight-mi355x -i <sequences.fa[.gz]> -o <out.aln> [--write-tree <tree.nwk>] [--tree-seeds S] [-m N] [flags of the first form; one GPU, no --host-staged]\n"
                                 "        (no -t: the guide tree is built from the k-mers the sequences share, at most 16384 sequences, and the run goes on as with -t on that tree;\n"
                                 "         --tree-seeds S builds it in two stages around S seed sequences, for more sequences than that: S near twice the square root of their number)\n"
-                                "       twilight-mi355x [-t <tree.nwk>] -i <sequences.fa[.gz]> -o <out.aln> --iterations K [--mask-gappy 0.95] [--write-tree <tree.nwk>] [scoring flags; one GPU]\n"
+                                "       twilight-mi355x [-t <tree.nwk>] -i <sequences.fa[.gz]> -o <out.aln> --iterations K [--mask-gappy 0.95] [--retree-seeds S] [--write-tree <tree.nwk>] [scoring flags; one GPU]\n"
                                 "        (K = 1 .. 5 runs: after every run but the last the guide tree is computed anew from the alignment, over the columns in which at most\n"
-                                "         the part --mask-gappy of the rows holds a gap; at most 16384 sequences; no -a, -f, -m, --filter, --host-staged; only the last alignment is written)\n";
+                                "         the part --mask-gappy of the rows holds a gap; at most 16384 sequences; no -a, -f, -m, --filter, --host-staged; only the last alignment is written;\n"
+                                "         --retree-seeds S computes those trees in two stages around S seed rows, for more sequences than that: S near twice the square root of their number)\n";
         return 1;
     }
 #ifdef TWL_GUIDE

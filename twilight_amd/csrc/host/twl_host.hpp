@@ -152,6 +152,7 @@ struct Option {
     std::string treeText;        // the built tree as Newick text: read in place of treeFile (openTree)
     int iterations = 1;          // --iterations K: the run is repeated K times, runs 2 .. K on a tree computed from the alignment of the run before (retree.cpp)
     double maskGappy = 0.95;     // --mask-gappy T: a column with more than floor(T * N) gaps does not enter that tree's distances
+    int retreeSeeds = 0;         // --retree-seeds S: those trees are built in two stages around S seed rows (retree.cpp); 0: in one
     // scoring flags (consumed by Params)
     float match = 18, mismatch = -8, transition = -4, gapOpen = -50, gapExtend = -5, xdrop = 600;
     bool hasGapEnds = false;
@@ -333,7 +334,7 @@ int runDefaultAlignment(Option &option, alnFunction kernel, alnFunction deferred
 // allowMerge: the binary carries the merge mode as well: -f/--files with -o and none of -t, -i, -a selects MERGE_MSA
 // allowSubtrees: the binary carries the subtree mode too: -m/--max-subtree N with -t, -i, -o sets Option::maxSubtree
 // allowGuide: the binary builds the guide tree itself when none is given: -i and -o without -t, -a or -f sets Option::buildTree
-//             ... and knows --iterations K and --mask-gappy T (retree.cpp); without it both are unsupported options
+//             ... and knows --iterations K, --mask-gappy T and --retree-seeds S (retree.cpp); without it all three are unsupported options
 bool parseCommandLine(int argc, char **argv, Option &option, bool allowPlacement = false, bool allowMerge = false, bool allowSubtrees = false, bool allowGuide = false);
 // The guide tree of a run: from option.treeText when the run built it, from the file option.treeFile otherwise; the same parser either way.
 Tree *openTree(const Option &option);
@@ -346,6 +347,7 @@ void refuseName(const std::string &name);
 // --iterations K, K >= 2 (retree.cpp, libtwl_host.so): the default alignment K times; after every run but the last the guide tree is computed anew
 // from the finished rows (pair counts on the device, include/twl_retree.h; distances, UPGMA and text on the host).  The first tree is the
 // user's (-t) or the k-mer tree.  Only the last alignment is written; option.writeTreeFile receives the tree it was built on.  Returns its length.
+// With option.retreeSeeds > 0 the trees are rebuilt in two stages (section 4j; include/twl_retree_set.h), for up to 2^20 sequences.
 int runIterations(Option &option);
 // PLACE_WO_TREE (place.cpp, libtwl_host.so): the sequences of option.seqFile placed into the alignment option.backboneAlnFile, written to
 // option.outFile.  Returns the final alignment length.

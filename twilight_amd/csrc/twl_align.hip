@@ -9,6 +9,7 @@
 #include "../../include/twl_subtree.h"
 #include "../../include/twl_guide.h"
 #include "../../include/twl_retree.h"
+#include "../../include/twl_retree_set.h"
 #include "../../include/twl_backbone.h"
 #include "level_kernels.hip.h"
 #include "restore_kernels.hip.h"
@@ -17,6 +18,7 @@
 #include "subtree_kernels.hip.h"
 #include "guide_kernels.hip.h"
 #include "retree_kernels.hip.h"
+#include "retree_stage_kernels.hip.h"
 #include "backbone_kernels.hip.h"
 #include "talco_kernel.hip.h"
 #include "talco_nuc.hip.h"
@@ -676,4 +678,5 @@ int twl_mt_tables(int device, twl_mt_dims *dims, int32_t *order, int32_t *anchor
 #include "twl_guide.inc.hip"
 #include "twl_guide_set.inc.hip"
 #include "twl_retree.inc.hip"
+#include "twl_retree_set.inc.hip"
 #include "twl_backbone.inc.hip"

@@ -115,12 +115,32 @@ bool parseCommandLine(int argc, char **argv, Option &o, bool allowPlacement, boo
             if (end == v || *end != '\0' || n < 2 || n > 16384) { std::cerr << "ERROR: --retree-seeds needs a number of seeds from 2 to 16384 (got " << v << ").\n"; exit(1); }
             o.retreeSeeds = (int)n;
         }
+        else if (allowGuide && flag(a, nullptr, "--adjust-direction")) o.adjustDirection = true;
+        else if (allowGuide && flag(a, nullptr, "--write-directions")) o.writeDirectionsFile = val();
+        else if (allowGuide && flag(a, nullptr, "--direction-seeds")) {
+            const char *v = val();
+            char *end = nullptr;
+            const long n = strtol(v, &end, 10);
+            if (end == v || *end != '\0' || n < 1 || n > 16384) { std::cerr << "ERROR: --direction-seeds needs a number of seeds from 1 to 16384 (got " << v << ").\n"; exit(1); }
+            o.directionSeeds = (int)n;
+        }
         else if (flag(a, nullptr, "--overwrite")) {}
         else if (flag(a, "-h", "--help")) return false;
         else { std::cerr << "ERROR: unsupported option " << a << " (this build covers the tree+sequences alignment mode only)\n"; exit(1); }
     }
     if (maskGiven && o.iterations < 2) { std::cerr << "ERROR: --mask-gappy applies to the trees that --iterations 2 or more rebuilds from an alignment.\n"; exit(1); }
     if (o.retreeSeeds > 0 && o.iterations < 2) { std::cerr << "ERROR: --retree-seeds applies to the trees that --iterations 2 or more rebuilds from an alignment.\n"; exit(1); }
+    if (!o.adjustDirection && (o.directionSeeds > 0 || !o.writeDirectionsFile.empty())) {
+        std::cerr << "ERROR: --direction-seeds and --write-directions apply to a run with --adjust-direction.\n";
+        exit(1);
+    }
+    if (o.adjustDirection) {               // directions (strand.cpp): decided on one GPU before anything else reads -i; the records of -i only
+        if (!o.msaDir.empty()) { std::cerr << "ERROR: --adjust-direction cannot be combined with -f: the rows of an alignment cannot be turned.\n"; exit(1); }
+        if (o.placeOnTree) { std::cerr << "ERROR: --adjust-direction is not available with --place-on-tree.\n"; exit(1); }
+        if (o.hostStaged) { std::cerr << "ERROR: --host-staged is not available with --adjust-direction (the directions are decided on the device).\n"; exit(1); }
+        if (o.gpuIdx.size() > 1 || o.gpuNum > 1) { std::cerr << "ERROR: --adjust-direction runs on one GPU: give at most one --gpu-index.\n"; exit(1); }
+        if (typeGiven && o.type != 'n') { std::cerr << "ERROR: --adjust-direction applies to nucleotide sequences (--type n): a protein has no reverse complement.\n"; exit(1); }
+    }
     if (o.iterations > 1) {                // iterations (retree.cpp): the tree+sequences run or the run that builds its tree, repeated on one GPU, rows device-resident
         if (!o.backboneAlnFile.empty() || !o.msaDir.empty() || subtreesGiven) { std::cerr << "ERROR: --iterations cannot be combined with -a, -f or -m.\n"; exit(1); }
         if (!o.noFilter) { std::cerr << "ERROR: --iterations cannot be combined with --filter: the rebuilt tree would lack the excluded sequences.\n"; exit(1); }
@@ -179,6 +199,10 @@ bool parseCommandLine(int argc, char **argv, Option &o, bool allowPlacement, boo
     if (o.gpuIdx.empty() && o.gpuNum > 0) for (int g = 0; g < o.gpuNum; ++g) o.gpuIdx.push_back(g);
     o.typeGiven = typeGiven;
     if (!typeGiven && o.alnMode != MERGE_MSA) o.type = io::detectType(o.seqFile);      // (a merge takes it from its first file: merge.cpp)
+    if (o.adjustDirection && o.type != 'n') {
+        std::cerr << "ERROR: --adjust-direction applies to nucleotide sequences; " << o.seqFile << " reads as protein (a protein has no reverse complement).\n";
+        exit(1);
+    }
     const int maxCpu = effectiveCpus();
     if (o.cpuNum <= 0 || o.cpuNum > maxCpu) o.cpuNum = maxCpu;       // -C/--cpu, default: all usable cores (option.cpp:41-46)
     omp_set_num_threads(o.cpuNum);

@@ -137,7 +137,7 @@ std::string buildGuideTree(Option &option)
         refuseName(name);
         names.push_back(name);
         seqs.push_back(std::move(seq));
-    });
+    }, &option);      // (oriented where --adjust-direction turned a record: the tree is built from what is aligned)
     const size_t N = names.size();
     if (N < 2) { std::cerr << "ERROR: a guide tree needs at least 2 sequences; " << option.seqFile << " holds " << N << ".\n"; exit(1); }
     if (option.treeSeeds > 0 && (size_t)option.treeSeeds > N) {

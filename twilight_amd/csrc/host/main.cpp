@@ -5,6 +5,7 @@
 //   twilight-mi355x -f DIR -o out.aln [...]                      (built with TWL_MERGE: the alignments of a directory merged, merge.cpp)
 //   twilight-mi355x -t tree.nwk -i seqs.fa -o out.aln -m N [...] (built with TWL_SUBTREE: the tree aligned in subtrees of at most N leaves, subtrees.cpp)
 //   twilight-mi355x -i seqs.fa -o out.aln [--write-tree t.nwk] [--tree-seeds S]   (built with TWL_GUIDE: no tree given, the guide tree is built from the sequences, guide.cpp)
+//   twilight-mi355x [-t tree.nwk | -a backbone.aln] -i seqs.fa -o out.aln --adjust-direction [--direction-seeds S] [--write-directions FILE]   (TWL_GUIDE: reverse-complemented records turned first, strand.cpp)
 //   twilight-mi355x [-t tree.nwk] -i seqs.fa -o out.aln --iterations K [--mask-gappy T] [--retree-seeds S]   (TWL_GUIDE: the run K times, the tree rebuilt from every alignment but the last, retree.cpp)
 #include "twl_host.hpp"
 
@@ -91,9 +92,14 @@ int main(int argc, char **argv)
                                 "        (K = 1 .. 5 runs: after every run but the last the guide tree is computed anew from the alignment, over the columns in which at most\n"
                                 "         the part --mask-gappy of the rows holds a gap; at most 16384 sequences; no -a, -f, -m, --filter, --host-staged; only the last alignment is written;\n"
                                 "         --retree-seeds S computes those trees in two stages around S seed rows, for more sequences than that: S near twice the square root of their number)\n";
+        if (guide) std::cerr << "       twilight-mi355x [-t <tree.nwk> | -a <backbone.aln>] -i <sequences.fa[.gz]> -o <out.aln> --adjust-direction [--direction-seeds S] [--write-directions <file>] [flags of that form; one GPU]\n"
+                                "        (nucleotides: records that lie reverse-complemented are found from the 6-mers they share with S seed sequences and with the seeds' reverse complements,\n"
+                                "         turned before anything else reads them and written as _R_<name>; S defaults to the smallest S with S * S >= 4 N; with -a the seeds are backbone rows and only\n"
+                                "         new sequences are turned; no -f, --place-on-tree, --host-staged; --write-directions lists name<TAB>+ or - per kept record, in input order)\n";
         return 1;
     }
 #ifdef TWL_GUIDE
+    if (option.adjustDirection) msa::adjustDirections(option);      // one process, one GPU (parseCommandLine refused more); every later read of -i sees the oriented records
     if (option.iterations > 1) {                     // one process, one GPU (parseCommandLine refused more); builds the first tree itself where none is given
         const auto ti = std::chrono::high_resolution_clock::now();
         const int W = msa::runIterations(option);
@@ -200,7 +206,7 @@ int main(int argc, char **argv)
             }
         });
     }
-    if (!option.buildTree) msa::progressive::gpu::beginInit(&option);      // (a run that built its tree has its device up already)
+    if (!option.buildTree && !option.adjustDirection) msa::progressive::gpu::beginInit(&option);      // (a run that built its tree or decided directions has its device up already)
     // exit handlers run last-registered first: registered again behind whatever the GPU runtime registered while it came up, the mark is set
     // BEFORE the runtime's own teardown, which may block while other ranks sit in a collective
     if (world > 1) atexit(markFailedAtExit);

@@ -185,7 +185,7 @@ int runPlacement(Option &option)
         std::vector<const std::string *> names;
         std::vector<const char *> rowAt;
         for (size_t k = 0; k < outIds.size(); ++k) { names.push_back(k < (size_t)B ? &bbNames[k] : &placed[k - B]->name); rowAt.push_back(&rows[k * (size_t)W]); }
-        io::writeRecords(option.outFile, names, rowAt, W);
+        io::writeRecords(option.outFile, names, rowAt, W, &option, (size_t)B);      // (only new sequences are ever turned)
     }
     tot.write = nowMs() - t;
     std::cerr << "Placed " << M << " sequences into " << B << " backbone rows: final alignment length " << W << " (backbone " << L << "), "

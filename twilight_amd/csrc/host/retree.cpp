@@ -193,7 +193,7 @@ int runIterations(Option &option)
     if (option.buildTree) {
         option.writeTreeFile.clear();      // (the tree that is written is the last one, below)
         option.treeText = buildGuideTree(option);
-    } else
+    } else if (!option.adjustDirection)      // (--adjust-direction has brought the device up already)
         progressive::gpu::beginInit(&option);
     alnFunction kernel = progressive::gpu::alignmentKernel_Resident;
     int alnLen = 0;

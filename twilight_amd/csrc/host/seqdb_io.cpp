@@ -1,6 +1,7 @@
 // twilight_amd/csrc/host/seqdb_io.cpp -- sequence storage, scoring parameters, FASTA in / MSA out.
 // Mirrors /root/reference/src/sequencedb.cpp, scoring-matrix.cpp, io.cpp (readSequences, writeAlignment) for DEFAULT_ALN.
 #include "twl_host.hpp"
+#include "strand_orient.hpp"
 
 #include <zlib.h>
 
@@ -339,14 +340,20 @@ static bool nextRecord(ChunkReader &in, std::string &carry, std::string &name, s
     }
 }
 
-void readRecords(const std::string &fileName, const std::function<void(std::string &, std::string &)> &each)
+// a record of -i that --adjust-direction found reversed is turned as soon as it is read: every reader sees the oriented text
+static inline void orient(const std::string &fileName, const Option *option, const std::string &name, std::string &seq)
+{
+    if (option && !option->reversedNames.empty() && fileName == option->seqFile && option->reversedNames.count(name)) strand::reverseComplement(seq);
+}
+
+void readRecords(const std::string &fileName, const std::function<void(std::string &, std::string &)> &each, const Option *option)
 {
     gzFile f = gzopen(fileName.c_str(), "r");
     if (!f) { fprintf(stderr, "ERROR: cant open file: %s\n", fileName.c_str()); exit(1); }
     gzbuffer(f, 1 << 22);
     ChunkReader in(f);
     std::string carry, name, seq;
-    while (nextRecord(in, carry, name, seq)) each(name, seq);
+    while (nextRecord(in, carry, name, seq)) { orient(fileName, option, name, seq); each(name, seq); }
     gzclose(f);
 }
 
@@ -404,6 +411,7 @@ void readSequences(const std::string &fileName, SequenceDB *database, Option *op
             printf("WARNING: duplicate leaf names found in the sequence file! Leaf name: %s. Only the first occurrence will be kept.\n", name.c_str());
             continue;
         }
+        orient(fileName, option, name, seq);
         const int L = (int)seq.size();
         maxLen = std::max(maxLen, L);
         minLen = std::min(minLen, L);
@@ -465,33 +473,34 @@ void readSequences(const std::string &fileName, SequenceDB *database, Option *op
               << (option->noFilter ? "Deferred sequences: " : "Excluded sequences: ") << numLowQ << '\n';
 }
 
-static void writeRow(std::ostream &out, const std::string &name, const char *row, int len)
+static void writeRow(std::ostream &out, const std::string &name, const char *row, int len, bool reversed = false)
 {
-    out << '>' << name << '\n';
+    out << '>' << (reversed ? "_R_" : "") << name << '\n';
     out.write(row, len);
     out << '\n';
 }
 
-void writeAlignment(const std::string &fileName, SequenceDB *database, int alnLen)     // io.cpp:512-525 (plain FASTA, input order)
+void writeAlignment(const std::string &fileName, SequenceDB *database, int alnLen, const Option *option)     // io.cpp:512-525 (plain FASTA, input order)
 {
     std::ofstream out(fileName, std::ios::binary);
     if (!out) { fprintf(stderr, "ERROR: Failed to open file: %s\n", fileName.c_str()); exit(1); }
     for (auto *s : database->sequences)
-        if (!s->lowQuality) writeRow(out, s->name, &s->alnStorage[s->storage][0], alnLen);
+        if (!s->lowQuality) writeRow(out, s->name, &s->alnStorage[s->storage][0], alnLen, option && option->reversedNames.count(s->name));
 }
 
-void writeRecords(const std::string &fileName, const std::vector<const std::string *> &names, const std::vector<const char *> &rows, int W)
+void writeRecords(const std::string &fileName, const std::vector<const std::string *> &names, const std::vector<const char *> &rows, int W, const Option *option,
+                  size_t firstRenamable)
 {
     std::ofstream out(fileName, std::ios::binary);
     if (!out) { fprintf(stderr, "ERROR: Failed to open file: %s\n", fileName.c_str()); exit(1); }
-    for (size_t k = 0; k < names.size(); ++k) writeRow(out, *names[k], rows[k], W);
+    for (size_t k = 0; k < names.size(); ++k) writeRow(out, *names[k], rows[k], W, option && k >= firstRenamable && option->reversedNames.count(*names[k]));
     if (!out) { fprintf(stderr, "ERROR: Failed to write file: %s\n", fileName.c_str()); exit(1); }
 }
 
 void writeFinalMSA(SequenceDB *database, Option *option, int alnLen)                  // io.cpp:465-488, DEFAULT_ALN branch
 {
     std::cerr << "Final Alignment Length: " << alnLen << '\n';
-    writeAlignment(option->outFile, database, alnLen);
+    writeAlignment(option->outFile, database, alnLen, option);
 }
 
 }  // namespace io

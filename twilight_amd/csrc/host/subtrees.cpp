@@ -224,7 +224,7 @@ int runSubtrees(Option &option)
     for (const Subtree &s : subs)
         for (const std::string &n : s.names) { rowAt.push_back(rows.data() + names.size() * (size_t)W); names.push_back(&n); }
     std::cerr << "Final Alignment Length: " << W << '\n';
-    io::writeRecords(option.outFile, names, rowAt, W);
+    io::writeRecords(option.outFile, names, rowAt, W, &option);
     tot.write = nowMs() - t;
     std::cerr << "Aligned " << G << " subtrees (" << nRows << " rows) and merged them: subtrees " << tot.pairsA << " pairs, " << tot.cellsA << " band cells; merge "
               << tot.level.run.cells << " band cells, " << tot.level.run.retries << " retried DP run(s)\n";

@@ -153,6 +153,10 @@ struct Option {
     int iterations = 1;          // --iterations K: the run is repeated K times, runs 2 .. K on a tree computed from the alignment of the run before (retree.cpp)
     double maskGappy = 0.95;     // --mask-gappy T: a column with more than floor(T * N) gaps does not enter that tree's distances
     int retreeSeeds = 0;         // --retree-seeds S: those trees are built in two stages around S seed rows (retree.cpp); 0: in one
+    bool adjustDirection = false;    // --adjust-direction: reverse-complemented records of -i are found from shared k-mers and turned before anything else reads them (strand.cpp)
+    int directionSeeds = 0;          // --direction-seeds S: the directions are decided against S seed sequences; 0: the smallest S with S * S >= 4 N
+    std::string writeDirectionsFile; // --write-directions: one "name<TAB>+|-" line per kept record, in input order
+    std::unordered_set<std::string> reversedNames;      // the records of seqFile that adjustDirections found reversed: read reverse-complemented, written as _R_<name>
     // scoring flags (consumed by Params)
     float match = 18, mismatch = -8, transition = -4, gapOpen = -50, gapExtend = -5, xdrop = 600;
     bool hasGapEnds = false;
@@ -214,16 +218,19 @@ struct SequenceDB {
 
 namespace io {
 void readSequences(const std::string &fileName, SequenceDB *database, Option *option, Tree *&T);
-void writeAlignment(const std::string &fileName, SequenceDB *database, int alnLen);
+void writeAlignment(const std::string &fileName, SequenceDB *database, int alnLen, const Option *option = nullptr);      // option: its reversedNames are written as _R_<name>
 void writeFinalMSA(SequenceDB *database, Option *option, int alnLen);
 char detectType(const std::string &seqFile);
 // every record of a FASTA(.gz) file, in file order, as readSequences sees them: each(name, sequence)
-void readRecords(const std::string &fileName, const std::function<void(std::string &, std::string &)> &each);
+// option: where fileName is its seqFile, the records named in its reversedNames arrive reverse-complemented
+void readRecords(const std::string &fileName, const std::function<void(std::string &, std::string &)> &each, const Option *option = nullptr);
 // every record of an alignment file (`kind`: "a backbone alignment", "an alignment"); returns the one length of its rows, -1 for a file without
 // records; rows of two lengths end the run
 int32_t readAlignedRows(const std::string &fileName, const char *kind, std::vector<std::string> &names, std::vector<std::string> &rows);
 // plain FASTA of rows that all have W columns: record k is names[k] and the W bytes at rows[k]
-void writeRecords(const std::string &fileName, const std::vector<const std::string *> &names, const std::vector<const char *> &rows, int W);
+// option: the records from firstRenamable on whose names are in its reversedNames are written as _R_<name>
+void writeRecords(const std::string &fileName, const std::vector<const std::string *> &names, const std::vector<const char *> &rows, int W, const Option *option = nullptr,
+                  size_t firstRenamable = 0);
 }  // namespace io
 
 using alnFunction = std::function<void(Tree *, NodePairVec &, SequenceDB *, Option *, Params &)>;
@@ -342,6 +349,10 @@ Tree *openTree(const Option &option);
 // Newick text, written to option.writeTreeFile when that is set.  Returns the text.
 // With option.treeSeeds > 0 the tree is built in two stages (section 4g): seeds, clusters around them, a tree per cluster grafted onto the seeds' tree.
 std::string buildGuideTree(Option &option);
+// --adjust-direction (strand.cpp, libtwl_host.so): the strand of every record of option.seqFile, decided on the device from the
+// k-mers it shares with seed sequences and with their reverse complements (include/twl_strand.h).  Fills option.reversedNames and writes
+// option.writeDirectionsFile; runs before anything else opens the input.  With -a the seeds are backbone rows, which are never turned.
+void adjustDirections(Option &option);
 // What buildGuideTree refuses about a sequence name (it could not be a leaf of a written tree): ends the run with a message.
 void refuseName(const std::string &name);
 // --iterations K, K >= 2 (retree.cpp, libtwl_host.so): the default alignment K times; after every run but the last the guide tree is computed anew

@@ -8,6 +8,7 @@
 #include "../../include/twl_merge.h"
 #include "../../include/twl_subtree.h"
 #include "../../include/twl_guide.h"
+#include "../../include/twl_strand.h"
 #include "../../include/twl_retree.h"
 #include "../../include/twl_retree_set.h"
 #include "../../include/twl_backbone.h"
@@ -677,6 +678,7 @@ int twl_mt_tables(int device, twl_mt_dims *dims, int32_t *order, int32_t *anchor
 #include "twl_subtree.inc.hip"
 #include "twl_guide.inc.hip"
 #include "twl_guide_set.inc.hip"
+#include "twl_strand.inc.hip"
 #include "twl_retree.inc.hip"
 #include "twl_retree_set.inc.hip"
 #include "twl_backbone.inc.hip"

@@ -10,6 +10,7 @@ struct twl_guide_set {
     Device *d = nullptr;
     GuideRun run;                                             // counts and w stay; letters, offsets and lengths leave after the count kernel
     double count_ms = 0, assign_ms = 0, groups_ms = 0, download_ms = 0;      // summed over the calls on this set
+    double permute_ms = 0, strand_assign_ms = 0, opposite_ms = 0, strand_download_ms = 0;      // ... and over the calls of twl_strand.inc.hip
 };
 
 namespace {

@@ -76,6 +76,8 @@ bool parseCommandLine(int argc, char **argv, Option &o, bool allowPlacement, boo
         else if (allowPlacement && flag(a, "-a", "--alignment")) o.backboneAlnFile = val();
         else if (allowPlacement && flag(a, nullptr, "--place-on-tree")) o.placeOnTree = true;
         else if (allowPlacement && flag(a, nullptr, "--test-place-chunk")) o.testPlaceChunk = std::max(0, atoi(val()));
+        else if (allowPlacement && flag(a, nullptr, "--keep-length")) o.keepLength = true;
+        else if (allowPlacement && flag(a, nullptr, "--write-insertions")) o.writeInsertionsFile = val();
         else if (allowMerge && flag(a, "-f", "--files")) o.msaDir = val();
         else if (allowSubtrees && flag(a, "-m", "--max-subtree")) {
             const char *v = val();
@@ -133,6 +135,13 @@ bool parseCommandLine(int argc, char **argv, Option &o, bool allowPlacement, boo
     if (!o.adjustDirection && (o.directionSeeds > 0 || !o.writeDirectionsFile.empty())) {
         std::cerr << "ERROR: --direction-seeds and --write-directions apply to a run with --adjust-direction.\n";
         exit(1);
+    }
+    if (!o.writeInsertionsFile.empty() && !o.keepLength) { std::cerr << "ERROR: --write-insertions applies to a run with --keep-length: only there are insertions left out.\n"; exit(1); }
+    if (o.keepLength) {                    // placement at the backbone's length (place.cpp): -a without a tree only
+        if (!o.msaDir.empty()) { std::cerr << "ERROR: --keep-length cannot be combined with -f: a merge has no backbone whose length could be kept.\n"; exit(1); }
+        if (o.placeOnTree) { std::cerr << "ERROR: --keep-length is not available with --place-on-tree: the backbone's groups are re-aligned there, so no backbone coordinate is kept.\n"; exit(1); }
+        if (o.backboneAlnFile.empty()) { std::cerr << "ERROR: --keep-length applies to placement into a backbone alignment: give it with -a.\n"; exit(1); }
+        if (!o.writeInsertionsFile.empty() && o.writeInsertionsFile == o.outFile) { std::cerr << "ERROR: --write-insertions names the same file as -o.\n"; exit(1); }
     }
     if (o.adjustDirection) {               // directions (strand.cpp): decided on one GPU before anything else reads -i; the records of -i only
         if (!o.msaDir.empty()) { std::cerr << "ERROR: --adjust-direction cannot be combined with -f: the rows of an alignment cannot be turned.\n"; exit(1); }

@@ -1,7 +1,8 @@
 // twilight_amd/csrc/host/main.cpp -- `twilight-mi355x`: TWILIGHT's tree+sequences mode with the MI355X level kernel.
 //   twilight-mi355x -t tree.nwk -i seqs.fa -o out.aln [-v] [--check] [--gpu-index 0,1,...] [scoring flags as in TWILIGHT]
 //   twilight-mi355x -a backbone.aln -i new.fa -o out.aln [...]   (built with TWL_PLACE: placement without a tree, place.cpp)
-//   twilight-mi355x -t tree.nwk -a backbone.aln -i new.fa -o out.aln --place-on-tree [...]   (TWL_PLACE: placement along the tree, place_tree.cpp)
+//   twilight-mi355x -a backbone.aln -i new.fa -o out.aln --keep-length [--write-insertions FILE] [...]   (TWL_PLACE: the backbone's columns kept, insertions left out, place.cpp)
+//   twilight-mi355x -t tree.nwk -a backbone.aln -i new.fa -o out.aln --place-on-tree [...] (TWL_PLACE: placement along the tree, place_tree.cpp)
 //   twilight-mi355x -f DIR -o out.aln [...]                      (built with TWL_MERGE: the alignments of a directory merged, merge.cpp)
 //   twilight-mi355x -t tree.nwk -i seqs.fa -o out.aln -m N [...] (built with TWL_SUBTREE: the tree aligned in subtrees of at most N leaves, subtrees.cpp)
 //   twilight-mi355x -i seqs.fa -o out.aln [--write-tree t.nwk] [--tree-seeds S]   (built with TWL_GUIDE: no tree given, the guide tree is built from the sequences, guide.cpp)
@@ -78,6 +79,9 @@ int main(int argc, char **argv)
         std::cerr << "usage: twilight-mi355x -t <tree.nwk> -i <sequences.fa[.gz]> -o <out.aln> [-r 0.95] [--type n|p] [--match 18 --mismatch -8 --transition -4\n"
                      "        --gap-open -50 --gap-extend -5 --gap-ends X --xdrop 600] [-w] [--rooted] [--filter] [--check] [-v] [--gpu-index 0,1] [--host-staged]\n";
         if (placement) std::cerr << "       twilight-mi355x -a <backbone.aln[.gz]> -i <new_sequences.fa[.gz]> -o <out.aln> [scoring and filtering flags as above] [--gpu-index 0]\n";
+        if (placement) std::cerr << "       twilight-mi355x -a <backbone.aln[.gz]> -i <new_sequences.fa[.gz]> -o <out.aln> --keep-length [--write-insertions <file>] [flags of the form above]\n"
+                                    "        (the backbone's columns stay as they are: its rows are written byte for byte, every new sequence at the backbone's length; the letters a new sequence\n"
+                                    "         has between two backbone columns are left out, and --write-insertions lists them as name<TAB>backbone columns in front<TAB>letters; no -f, --place-on-tree)\n";
         if (placement) std::cerr << "       twilight-mi355x -t <tree.nwk> -a <backbone.aln[.gz]> -i <new_sequences.fa[.gz]> -o <out.aln> --place-on-tree [flags of the first form; one GPU, no --host-staged, no -m]\n"
                                     "        (the tree holds the backbone's rows and the new sequences; the backbone falls into groups along the tree, which are re-aligned against each other)\n";
         if (merging) std::cerr << "       twilight-mi355x -f <directory of alignments (.gz too), searched recursively> -o <out.aln> [scoring flags as above] [-r 0.95] [--type n|p] [-v] [--gpu-index 0]\n"

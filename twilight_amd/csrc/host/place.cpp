@@ -7,15 +7,20 @@
 //   chunks of new sequences       -> twl_level_prepare / twl_level_align / twl_level_restore, unchanged (include/twl_level.h)
 //   twl_place_collect             -> their final paths kept in HBM, the longest insertion per backbone slot (mergeInsertions)
 //   twl_place_finish              -> every row at the final width (io.cpp:355-449), read back once and written
+// With --keep-length (include/twl_keep.h) the last step is twl_place_finish_keep instead: the placed sequences become rows of the
+// backbone's own length, their insertions are left out (and listed with --write-insertions); the backbone rows are written from the host copy, which
+// is kept in this mode, and only the placed rows are read back.
 // Two deliberate differences from the reference: a backbone row of another length is refused (the reference warns and writes the row at
 // its own width), and the output order is fixed: the backbone rows in file order, then the placed sequences in input order (the reference
 // concatenates its temporary files by shell glob).
 #include "align_gpu.hpp"
 
 #include "../../../include/twl_place.h"
+#include "../../../include/twl_keep.h"
 
 #include <algorithm>
 #include <cstdio>
+#include <fstream>
 #include <iostream>
 #include <numeric>
 #include <string>
@@ -36,7 +41,83 @@ namespace {
 constexpr double kChunkBudget = 16.0 * (1 << 30);
 constexpr int kMaxChunk = 4096;
 
-struct Totals { double count = 0, dp = 0, restore = 0, collect = 0, finish = 0, read = 0, write = 0; progressive::gpu::DpTotals run; int restoredOnHost = 0; };
+struct Totals { double count = 0, dp = 0, restore = 0, collect = 0, finish = 0, runs = 0, read = 0, write = 0; progressive::gpu::DpTotals run; int restoredOnHost = 0; };
+
+// The finish of --keep-length (include/twl_keep.h): the placed sequences become rows of the backbone's length L on the device and are read back; the backbone
+// rows are written from the host copy as they were read; the runs of letters left out are counted, and listed where --write-insertions asks for them.
+// Ends the placement and the store.  Returns L.
+int finishKeepingLength(Option &option, twl_store *st, twl_place *pl, int32_t L, const std::vector<std::string> &bbNames, const std::vector<std::string> &bbRows,
+                        const std::vector<SequenceDB::SequenceInfo *> &placed, Totals &tot, int32_t nChunks, int32_t chunk)
+{
+    const int32_t B = (int32_t)bbRows.size(), M = (int32_t)placed.size();
+    int rc;
+    double t;
+    std::vector<int32_t> collected;                    // store ids with a path, in input order (an empty sequence has none when L is 0)
+    for (int32_t k = 0; k < M; ++k) if (placed[k]->len > 0 || L > 0) collected.push_back(B + k);
+    const int32_t nC = (int32_t)collected.size();
+    int64_t runs = 0, letters = 0;
+    t = nowMs();
+    if ((rc = twl_place_finish_keep(pl, &runs, &letters)) != TWL_OK) die("twl_place_finish_keep", rc);
+    tot.finish = nowMs() - t;
+    t = nowMs();
+    std::vector<int32_t> longest((size_t)L + 1), nRuns((size_t)nC), nLetters((size_t)nC);
+    if ((rc = twl_place_read_insertions(pl, longest.data())) != TWL_OK) die("twl_place_read_insertions", rc);
+    int64_t merged = L;
+    for (int32_t v : longest) merged += v;
+    if ((rc = twl_place_dropped_counts(pl, nC, collected.data(), nRuns.data(), nLetters.data())) != TWL_OK) die("twl_place_dropped_counts", rc);
+    int32_t withRuns = 0;
+    std::vector<int64_t> runOff((size_t)nC + 1, 0);
+    for (int32_t i = 0; i < nC; ++i) { runOff[i + 1] = runOff[i] + nRuns[i]; withRuns += nRuns[i] > 0; }
+    if (!option.writeInsertionsFile.empty()) {
+        std::vector<int32_t> col((size_t)runOff[nC] + 1), qpos((size_t)runOff[nC] + 1), len((size_t)runOff[nC] + 1);
+        if ((rc = twl_place_dropped_runs(pl, nC, collected.data(), runOff.data(), col.data(), qpos.data(), len.data())) != TWL_OK) die("twl_place_dropped_runs", rc);
+        std::ofstream ins(option.writeInsertionsFile, std::ios::binary);
+        if (!ins) { std::cerr << "ERROR: Failed to open file: " << option.writeInsertionsFile << '\n'; exit(1); }
+        for (int32_t i = 0; i < nC; ++i) {
+            const auto *s = placed[collected[i] - B];
+            const bool reversed = option.reversedNames.count(s->name) > 0;
+            for (int64_t r = runOff[i]; r < runOff[i + 1]; ++r) {
+                if (qpos[r] < 0 || len[r] < 1 || (int64_t)qpos[r] + len[r] > s->len) { std::cerr << "ERROR: a dropped run of " << s->name << " lies outside its sequence.\n"; exit(1); }
+                ins << (reversed ? "_R_" : "") << s->name << '\t' << col[r] << '\t';
+                ins.write(s->alnStorage[0] + qpos[r], len[r]);
+                ins << '\n';
+            }
+        }
+        ins.close();
+        if (!ins) { std::cerr << "ERROR: Failed to write file: " << option.writeInsertionsFile << '\n'; exit(1); }
+    }
+    tot.runs = nowMs() - t;
+    double rowsKernelMs = 0, runsKernelMs = 0;
+    (void)twl_place_keep_timing(pl, &rowsKernelMs, &runsKernelMs);
+    t = nowMs();
+    std::vector<int32_t> outIds((size_t)M), outLen((size_t)M);
+    std::iota(outIds.begin(), outIds.end(), B);
+    std::vector<char> rows((size_t)M * (size_t)L + 1);
+    if ((rc = twl_store_read_rows_of(st, M, outIds.data(), rows.data(), outLen.data())) != TWL_OK) die("twl_store_read_rows_of", rc);
+    for (int32_t k = 0; k < M; ++k)
+        if (outLen[k] != L) { std::cerr << "ERROR: the row of " << placed[k]->name << " has " << outLen[k] << " columns, not the backbone's " << L << ".\n"; exit(1); }
+    tot.read = nowMs() - t;
+    twl_place_destroy(pl);
+    twl_store_destroy(st);
+    t = nowMs();
+    {
+        std::vector<const std::string *> names;
+        std::vector<const char *> rowAt;
+        for (int32_t k = 0; k < B; ++k) { names.push_back(&bbNames[k]); rowAt.push_back(bbRows[k].data()); }
+        for (int32_t k = 0; k < M; ++k) { names.push_back(&placed[k]->name); rowAt.push_back(&rows[(size_t)k * (size_t)L]); }
+        io::writeRecords(option.outFile, names, rowAt, L, &option, (size_t)B);      // (only new sequences are ever turned)
+    }
+    tot.write = nowMs() - t;
+    std::cerr << "Placed " << M << " sequences into " << B << " backbone rows: final alignment length " << L << " (backbone " << L << "), "
+              << nChunks << " chunk(s) of at most " << chunk << ", " << tot.run.retries << " retried DP run(s)\n";
+    std::cerr << "Kept the backbone's length " << L << ": " << runs << " insertion run(s), " << letters << " letter(s) of " << withRuns
+              << " sequence(s) left out (merged they would make " << merged << " columns)\n";
+    if (option.printDetail)
+        fprintf(stderr, "Placement phases (ms): count %.3f, prepare+DP %.3f, restore %.3f, collect %.3f, keep-finish %.3f, runs %.3f, read-back %.3f, write %.3f; "
+                        "DP kernel %.3f ms, %llu band cells; restored on the host %d; keep kernels: rows %.3f ms, runs %.3f ms\n", tot.count, tot.dp, tot.restore,
+                tot.collect, tot.finish, tot.runs, tot.read, tot.write, tot.run.kernel, (unsigned long long)tot.run.cells, tot.restoredOnHost, rowsKernelMs, runsKernelMs);
+    return L;
+}
 
 }  // namespace
 
@@ -82,7 +163,7 @@ int runPlacement(Option &option)
     twl_store *st = nullptr;
     int rc = twl_store_create(device, option.type, B + M, rowPtr.data(), rowLen.data(), &st);
     if (rc != TWL_OK) die("twl_store_create", rc);
-    for (auto &r : bbRows) std::string().swap(r);
+    if (!option.keepLength) for (auto &r : bbRows) std::string().swap(r);      // (--keep-length writes the backbone from these very bytes)
     std::vector<int32_t> bbIds(B);
     std::iota(bbIds.begin(), bbIds.end(), 0);
     double t = nowMs();
@@ -165,6 +246,8 @@ int runPlacement(Option &option)
                 runLevel(std::vector<int32_t>{ids[i]}, tz, &e1);
             }
     }
+
+    if (option.keepLength) return finishKeepingLength(option, st, pl, L, bbNames, bbRows, placed, tot, nChunks, chunk);      // 
 
     // ---- merged insertions, final rows, output ----
     int32_t W = 0;

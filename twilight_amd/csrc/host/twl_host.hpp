@@ -144,6 +144,8 @@ struct Option {
     std::string backboneAlnFile; // -a / --alignment: the existing alignment new sequences are placed into (alnMode PLACE_WO_TREE; with -t and --place-on-tree PLACE_W_TREE)
     bool placeOnTree = false;    // --place-on-tree: -a together with -t places the new sequences along the tree (place_tree.cpp)
     int testPlaceChunk = 0;      // --test-place-chunk n: placement aligns at most n sequences per level (default: sized to device memory)
+    bool keepLength = false;     // --keep-length: placement (-a) leaves the backbone's columns as they are; the insertions of the new sequences are left out (place.cpp)
+    std::string writeInsertionsFile; // --write-insertions: one "name<TAB>k<TAB>letters" line per run of letters --keep-length left out
     std::string msaDir;          // -f / --files: a directory of alignments to merge into one (alnMode MERGE_MSA)
     bool typeGiven = false;      // --type was given (a merge detects the type from its first file otherwise)
     bool buildTree = false;      // -i and -o without -t, -a or -f: the guide tree is built from the sequences (guide.cpp)

@@ -5,6 +5,7 @@
 #include "../../include/twl_align.h"
 #include "../../include/twl_level.h"
 #include "../../include/twl_place.h"
+#include "../../include/twl_keep.h"
 #include "../../include/twl_merge.h"
 #include "../../include/twl_subtree.h"
 #include "../../include/twl_guide.h"
@@ -15,6 +16,7 @@
 #include "level_kernels.hip.h"
 #include "restore_kernels.hip.h"
 #include "place_kernels.hip.h"
+#include "keep_kernels.hip.h"
 #include "merge_kernels.hip.h"
 #include "subtree_kernels.hip.h"
 #include "guide_kernels.hip.h"
@@ -674,6 +676,7 @@ int twl_mt_tables(int device, twl_mt_dims *dims, int32_t *order, int32_t *anchor
 #include "twl_store.inc.hip"
 #include "twl_level.inc.hip"
 #include "twl_place.inc.hip"
+#include "twl_keep.inc.hip"
 #include "twl_merge.inc.hip"
 #include "twl_subtree.inc.hip"
 #include "twl_guide.inc.hip"

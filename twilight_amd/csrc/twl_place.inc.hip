@@ -8,16 +8,19 @@
 // and reads back.
 
 #include "twl_place_plan.inc.hip"
+#include "twl_keep_plan.inc.hip"
 
 struct twl_place {
     twl_store *s = nullptr;
     PlaceBook b;
-    Buf arena, longest, ins, colsrc, w, bad, hostRows;
+    KeepBook k;                      // the finish that keeps the backbone's length (twl_keep.inc.hip)
+    Buf arena, longest, ins, colsrc, w, bad, hostRows, keepCnt, keepRec;
+    double keepRowsMs = 0, keepRunsMs = 0;
     Arena up;                        // the small per-call tables of collect / finish: both synchronise the stream before they return
     PinBuf back;
     void release()
     {
-        for (Buf *buf : {&arena, &longest, &ins, &colsrc, &w, &bad, &hostRows}) buf->release();
+        for (Buf *buf : {&arena, &longest, &ins, &colsrc, &w, &bad, &hostRows, &keepCnt, &keepRec}) buf->release();
         up.release(); back.release();
     }
 };
@@ -144,6 +147,7 @@ int twl_place_finish(twl_place *pl, int32_t n_backbone, const int32_t *backbone_
     if (!pl || !W_out) { g_err = "bad argument"; return TWL_ERR_BAD_ARGUMENT; }
     twl_store *s = pl->s;
     PlaceBook &b = pl->b;
+    if (const char *why = check_finish_after_keep(pl->k)) { g_err = why; return TWL_ERR_BAD_ARGUMENT; }
     if (const char *why = check_place_finish(b, n_backbone, backbone_ids, s->n_seqs, s->len.data())) { g_err = why; return TWL_ERR_BAD_ARGUMENT; }
     const int32_t L = b.L;
     DEVICE_CALL(call, s->d);

@@ -88,4 +88,22 @@ inline double nowMs() { return std::chrono::duration<double, std::milli>(std::ch
 
 }  // namespace gpu
 }  // namespace progressive
+
+// ---- --trim-gappy / --trim-to (trim.cpp; include/twl_trim.h): the rows that are written lose their gappy columns on the device ----
+// One decision for every mode: twl_store_trim_columns over the n rows `ids` of a store, which are the rows that are written, in that order
+// (writtenName(k): the name row k is written under).  Either on the run's own store, between its last kernel and its read-back (resident), or
+// on a store made for it from the final host rows.  Ends the run, before any file is written, when --trim-to names no written row or no column is kept;
+// writes --write-columns.  What it returns goes to reportTrim once the trimmed rows are on the host (rowAt(k): the kept bytes of row k).
+struct TrimReport { int32_t W = 0, kept = 0, rows = 0, limit = 0; double kernelMs = 0; bool resident = true; };
+TrimReport trimStoreRows(const Option &option, twl_store *st, int32_t n, const int32_t *ids, const std::function<std::string(int32_t)> &writtenName, bool resident);
+void reportTrim(const Option &option, const TrimReport &r, const std::function<const char *(int32_t)> &rowAt);
+// ... and the read-back of those rows behind it (merge.cpp, subtrees.cpp, place.cpp): rows = the n trimmed rows back to back.  Returns the kept length.
+int32_t trimAndReadRows(const Option &option, twl_store *st, int32_t n, const int32_t *ids, const std::function<std::string(int32_t)> &writtenName, std::vector<char> &rows);
+// Rows that exist on the host only (n rows of W bytes): uploaded into a store of their own, trimmed there, read back into `out` back to back.  Returns the kept length.
+int32_t trimHostRows(Option &option, const std::vector<const char *> &rows, int32_t W, const std::function<std::string(int32_t)> &writtenName, std::vector<char> &out);
+// The same for the finished rows of a SequenceDB (what writeAlignment writes: the sequences that are not low-quality): trimmed in place.  Returns the kept length.
+int trimDatabaseRows(SequenceDB *database, Option *option, int alnLen);
+// The name a sequence of option.seqFile is written under: _R_<name> where --adjust-direction turned it.
+inline std::string writtenNameOf(const Option &option, const std::string &name) { return (option.reversedNames.count(name) ? "_R_" : "") + name; }
+
 }  // namespace msa

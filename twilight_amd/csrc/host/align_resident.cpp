@@ -103,6 +103,15 @@ void materialise(Tree *T, SequenceDB *db, Option *option)
     if (!firstStore(ctx)) return;
     const double t0 = nowMs();
     const int n = (int)db->sequences.size();
+    // A run whose output is trimmed (--trim-gappy, --trim-to): in the download that is the run's last the rows lose their columns here, on the
+    // device, so that only kept columns come back -- unless the host still needs whole rows (--check reads them, a compressed group's members
+    // wait for updateAlignment) or there are several replicas; the driver then trims an uploaded copy of the final rows.
+    std::function<void()> trimmedRowsAreBack;
+    if (db->trimRequested && db->lastDownload && option->trimResidentRows && ctx.stores.size() == 1 && !option->debug) {
+        bool whole = true;
+        for (const auto *s : db->sequences) whole = whole && s->subtreeIdx >= -1;
+        if (whole) trimmedRowsAreBack = option->trimResidentRows(db, option, firstStore(ctx));
+    }
     std::vector<int32_t> lens(n);
     int rc = twl_store_read_rows(firstStore(ctx), nullptr, lens.data());
     if (rc != TWL_OK) die("twl_store_read_rows", rc);
@@ -128,6 +137,7 @@ void materialise(Tree *T, SequenceDB *db, Option *option)
     rc = twl_store_read_rows(firstStore(ctx), rows.data(), lens.data());
     if (rc != TWL_OK) die("twl_store_read_rows", rc);
     for (int i = 0; i < n; ++i) db->sequences[i]->len = lens[i];
+    if (trimmedRowsAreBack) trimmedRowsAreBack();
     const int P = (option->type == 'n') ? 6 : 22;
     std::vector<Node *> keep{T->root};
     keep.insert(keep.end(), db->fallback_nodes.begin(), db->fallback_nodes.end());

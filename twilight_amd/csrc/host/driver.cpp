@@ -32,9 +32,9 @@ static int effectiveCpus()
 
 static bool flag(const char *a, const char *s, const char *l) { return (s && !strcmp(a, s)) || (l && !strcmp(a, l)); }
 
-bool parseCommandLine(int argc, char **argv, Option &o, bool allowPlacement, bool allowMerge, bool allowSubtrees, bool allowGuide)
+bool parseCommandLine(int argc, char **argv, Option &o, bool allowPlacement, bool allowMerge, bool allowSubtrees, bool allowGuide, bool allowTrim)
 {
-    bool typeGiven = false, subtreesGiven = false, maskGiven = false;
+    bool typeGiven = false, subtreesGiven = false, maskGiven = false, trimGappyGiven = false, trimToGiven = false;
     o.cpuNum = 0;
     for (int i = 1; i < argc; ++i) {
         const char *a = argv[i];
@@ -126,6 +126,16 @@ bool parseCommandLine(int argc, char **argv, Option &o, bool allowPlacement, boo
             if (end == v || *end != '\0' || n < 1 || n > 16384) { std::cerr << "ERROR: --direction-seeds needs a number of seeds from 1 to 16384 (got " << v << ").\n"; exit(1); }
             o.directionSeeds = (int)n;
         }
+        else if (allowTrim && flag(a, nullptr, "--trim-gappy")) {
+            const char *v = val();
+            char *end = nullptr;
+            const double t = strtod(v, &end);
+            if (end == v || *end != '\0' || !(t >= 0.0 && t <= 1.0)) { std::cerr << "ERROR: --trim-gappy needs a value in [0, 1] (got " << v << ").\n"; exit(1); }
+            o.trimGappy = t;
+            trimGappyGiven = true;
+        }
+        else if (allowTrim && flag(a, nullptr, "--trim-to")) { o.trimToName = val(); trimToGiven = true; }
+        else if (allowTrim && flag(a, nullptr, "--write-columns")) o.writeColumnsFile = val();
         else if (flag(a, nullptr, "--overwrite")) {}
         else if (flag(a, "-h", "--help")) return false;
         else { std::cerr << "ERROR: unsupported option " << a << " (this build covers the tree+sequences alignment mode only)\n"; exit(1); }
@@ -142,6 +152,15 @@ bool parseCommandLine(int argc, char **argv, Option &o, bool allowPlacement, boo
         if (o.placeOnTree) { std::cerr << "ERROR: --keep-length is not available with --place-on-tree: the backbone's groups are re-aligned there, so no backbone coordinate is kept.\n"; exit(1); }
         if (o.backboneAlnFile.empty()) { std::cerr << "ERROR: --keep-length applies to placement into a backbone alignment: give it with -a.\n"; exit(1); }
         if (!o.writeInsertionsFile.empty() && o.writeInsertionsFile == o.outFile) { std::cerr << "ERROR: --write-insertions names the same file as -o.\n"; exit(1); }
+    }
+    if (trimGappyGiven && trimToGiven) { std::cerr << "ERROR: --trim-gappy and --trim-to cannot be combined: one rule decides the columns.\n"; exit(1); }
+    if (!o.writeColumnsFile.empty() && !trimGappyGiven && !trimToGiven) { std::cerr << "ERROR: --write-columns applies to a run with --trim-gappy or --trim-to: only there are columns left out.\n"; exit(1); }
+    if (trimGappyGiven || trimToGiven) {   // the output without its gappy columns (trim.cpp): decided on one GPU over the rows that are written
+        if (!o.writeColumnsFile.empty() && o.writeColumnsFile == o.outFile) { std::cerr << "ERROR: --write-columns names the same file as -o.\n"; exit(1); }
+        if (o.keepLength) { std::cerr << "ERROR: --trim-gappy and --trim-to cannot be combined with --keep-length: its backbone rows are written from the host and never enter the trim.\n"; exit(1); }
+        if (o.hostStaged) { std::cerr << "ERROR: --host-staged is not available with --trim-gappy or --trim-to (the columns are decided on the device).\n"; exit(1); }
+        if (o.gpuIdx.size() > 1 || o.gpuNum > 1) { std::cerr << "ERROR: --trim-gappy and --trim-to run on one GPU: give at most one --gpu-index.\n"; exit(1); }
+        o.trimRule = trimToGiven ? 1 : 0;
     }
     if (o.adjustDirection) {               // directions (strand.cpp): decided on one GPU before anything else reads -i; the records of -i only
         if (!o.msaDir.empty()) { std::cerr << "ERROR: --adjust-direction cannot be combined with -f: the rows of an alignment cannot be turned.\n"; exit(1); }
@@ -230,6 +249,7 @@ int runDefaultAlignment(Option &option, alnFunction kernel, alnFunction deferred
     const double t0 = clk();
     SequenceDB database;
     database.updateSeqTh = option.updateSeqTh;
+    database.trimRequested = writeOutput && option.trimRule >= 0;           // (of --iterations only the run that is written carries it)
     Params param(option, option.type);
     Tree *T = openTree(option);                                             // twilight-main.cpp:122
     phylogeny::assignSinglePartition(T->root);                              // :129-130 with maxSubtree = INT32_MAX
@@ -241,7 +261,12 @@ int runDefaultAlignment(Option &option, alnFunction kernel, alnFunction deferred
     progressive::msaOnSubtree(subT, &database, &option, param, kernel, deferredKernel);   // :148
     const double t3 = clk();
     if (option.debug && !database.debug()) std::cerr << "WARNING: --check found an illegal alignment row.\n";
-    const int alnLen = subT->root->getAlnLen(database.currentTask);
+    int alnLen = subT->root->getAlnLen(database.currentTask);
+    if (database.trimRequested) {          // the rows lost their gappy columns in the last download, or lose them now on an uploaded copy (trim.cpp)
+        if (database.trimmedLen >= 0) alnLen = database.trimmedLen;
+        else if (option.trimHostRows) alnLen = option.trimHostRows(&database, &option, alnLen);
+        else { std::cerr << "ERROR: this build cannot trim the alignment.\n"; exit(1); }
+    }
     if (writeOutput) io::writeFinalMSA(&database, &option, alnLen);        // :165
     if (option.printDetail)
         std::cerr << "Driver phases (s): tree " << t1 - t0 << ", read " << t2 - t1 << ", align " << t3 - t2 << ", write " << clk() - t3 << '\n';

@@ -75,7 +75,12 @@ int main(int argc, char **argv)
 #else
     const bool guide = false;
 #endif
-    if (!msa::parseCommandLine(argc, argv, option, placement, merging, subtrees, guide)) {
+#ifdef TWL_TRIM
+    const bool trim = true;
+#else
+    const bool trim = false;
+#endif
+    if (!msa::parseCommandLine(argc, argv, option, placement, merging, subtrees, guide, trim)) {
         std::cerr << "usage: twilight-mi355x -t <tree.nwk> -i <sequences.fa[.gz]> -o <out.aln> [-r 0.95] [--type n|p] [--match 18 --mismatch -8 --transition -4\n"
                      "        --gap-open -50 --gap-extend -5 --gap-ends X --xdrop 600] [-w] [--rooted] [--filter] [--check] [-v] [--gpu-index 0,1] [--host-staged]\n";
         if (placement) std::cerr << "       twilight-mi355x -a <backbone.aln[.gz]> -i <new_sequences.fa[.gz]> -o <out.aln> [scoring and filtering flags as above] [--gpu-index 0]\n";
@@ -100,8 +105,14 @@ int main(int argc, char **argv)
                                 "        (nucleotides: records that lie reverse-complemented are found from the 6-mers they share with S seed sequences and with the seeds' reverse complements,\n"
                                 "         turned before anything else reads them and written as _R_<name>; S defaults to the smallest S with S * S >= 4 N; with -a the seeds are backbone rows and only\n"
                                 "         new sequences are turned; no -f, --place-on-tree, --host-staged; --write-directions lists name<TAB>+ or - per kept record, in input order)\n";
+        if (trim) std::cerr << "       every form above but --keep-length: [--trim-gappy T | --trim-to NAME] [--write-columns <file>]   (one GPU, no --host-staged)\n"
+                               "        (the alignment is written without its gappy columns: --trim-gappy keeps the columns in which at most floor(T * N) of the N written rows hold '-',\n"
+                               "         T in [0, 1]; --trim-to keeps the columns in which the written row called NAME holds a letter; --write-columns lists new<TAB>old<TAB>gaps per kept column)\n";
         return 1;
     }
+#ifdef TWL_TRIM
+    msa::enableTrim(option);
+#endif
 #ifdef TWL_GUIDE
     if (option.adjustDirection) msa::adjustDirections(option);      // one process, one GPU (parseCommandLine refused more); every later read of -i sees the oriented records
     if (option.iterations > 1) {                     // one process, one GPU (parseCommandLine refused more); builds the first tree itself where none is given

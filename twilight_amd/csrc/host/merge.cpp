@@ -155,6 +155,14 @@ int runMerge(Option &option)
         std::cerr << '[' << k + 1 << '/' << paths.size() << "] " << fs::path(f.path).filename().string() << " (Count: " << f.rows.size() << ", Length: " << f.L << ")\n";
     }
     const int32_t G = (int32_t)files.size();
+    if (G == 1 && option.trimRule >= 0) {      // nothing to merge, but columns to leave out: the file's rows through a store of their own (trim.cpp)
+        std::vector<const char *> rowPtr;
+        for (const std::string &r : files[0].rows) rowPtr.push_back(r.data());
+        std::vector<char> rows;
+        const int32_t kept = trimHostRows(option, rowPtr, files[0].L, [&](int32_t k) { return files[0].names[(size_t)k]; }, rows);
+        writeRecords(option.outFile, files, rows.data(), kept);
+        return kept;
+    }
     if (G == 1) {      // nothing to merge: the file comes back as it is
         writeRecords(option.outFile, files, nullptr, files[0].L);
         return files[0].L;
@@ -216,8 +224,15 @@ int runMerge(Option &option)
     tot.finish = nowMs() - t;
     t = nowMs();
     std::vector<int32_t> outLen((size_t)nRows);
-    std::vector<char> rows((size_t)nRows * (size_t)W + 1);
-    if ((rc = twl_store_read_rows_of(st, nRows, rowIds.data(), rows.data(), outLen.data())) != TWL_OK) die("twl_store_read_rows_of", rc);
+    std::vector<char> rows;
+    if (option.trimRule >= 0) {            // the rows lose their gappy columns on the device first (trim.cpp): W is the kept length from here on
+        std::vector<const std::string *> nameOf;
+        for (const MsaFile &f : files) for (const std::string &nm : f.names) nameOf.push_back(&nm);
+        W = trimAndReadRows(option, st, nRows, rowIds.data(), [&](int32_t k) { return *nameOf[(size_t)k]; }, rows);
+    } else {
+        rows.resize((size_t)nRows * (size_t)W + 1);
+        if ((rc = twl_store_read_rows_of(st, nRows, rowIds.data(), rows.data(), outLen.data())) != TWL_OK) die("twl_store_read_rows_of", rc);
+    }
     tot.read = nowMs() - t;
     twl_merge_destroy(mg);
     twl_store_destroy(st);

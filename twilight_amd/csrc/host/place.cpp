@@ -258,8 +258,15 @@ int runPlacement(Option &option)
     std::vector<int32_t> outIds(bbIds);
     for (int32_t k = 0; k < M; ++k) outIds.push_back(B + k);
     std::vector<int32_t> outLen(outIds.size());
-    std::vector<char> rows((size_t)outIds.size() * (size_t)W + 1);
-    if ((rc = twl_store_read_rows_of(st, (int32_t)outIds.size(), outIds.data(), rows.data(), outLen.data())) != TWL_OK) die("twl_store_read_rows_of", rc);
+    std::vector<char> rows;
+    const int32_t mergedW = W;
+    if (option.trimRule >= 0)              // the rows lose their gappy columns on the device first (trim.cpp): W is the kept length from here on
+        W = trimAndReadRows(option, st, (int32_t)outIds.size(), outIds.data(),
+                            [&](int32_t k) { return k < B ? bbNames[(size_t)k] : writtenNameOf(option, placed[(size_t)(k - B)]->name); }, rows);      // (only new sequences are ever turned)
+    else {
+        rows.resize((size_t)outIds.size() * (size_t)W + 1);
+        if ((rc = twl_store_read_rows_of(st, (int32_t)outIds.size(), outIds.data(), rows.data(), outLen.data())) != TWL_OK) die("twl_store_read_rows_of", rc);
+    }
     tot.read = nowMs() - t;
     twl_place_destroy(pl);
     twl_store_destroy(st);
@@ -271,7 +278,7 @@ int runPlacement(Option &option)
         io::writeRecords(option.outFile, names, rowAt, W, &option, (size_t)B);      // (only new sequences are ever turned)
     }
     tot.write = nowMs() - t;
-    std::cerr << "Placed " << M << " sequences into " << B << " backbone rows: final alignment length " << W << " (backbone " << L << "), "
+    std::cerr << "Placed " << M << " sequences into " << B << " backbone rows: final alignment length " << mergedW << " (backbone " << L << "), "
               << nChunks << " chunk(s) of at most " << chunk << ", " << tot.run.retries << " retried DP run(s)\n";
     if (option.printDetail)
         fprintf(stderr, "Placement phases (ms): count %.3f, prepare+DP %.3f, restore %.3f, collect %.3f, finish %.3f, read-back %.3f, write %.3f; "

@@ -116,6 +116,7 @@ int runPlacementOnTree(Option &option)
     const double t0 = nowMs();
     SequenceDB database;
     database.updateSeqTh = option.updateSeqTh;
+    database.trimRequested = option.trimRule >= 0;
     Params param(option, option.type);
     Tree *T = openTree(option);                                              // twilight-main.cpp:238
     phylogeny::assignSinglePartition(T->root);                               // :239-240 without -m
@@ -156,12 +157,14 @@ int runPlacementOnTree(Option &option)
     subT->root->alnWeight = placementT->root->alnWeight;
     const double t2 = nowMs();
     if (option.debug && !database.debug()) std::cerr << "WARNING: --check found an illegal alignment row.\n";
-    const int alnLen = subT->root->getAlnLen(database.currentTask);
-    io::writeFinalMSA(&database, &option, alnLen);                            // :280: database order -- backbone rows in file order, then the new sequences
+    int alnLen = subT->root->getAlnLen(database.currentTask);
+    const int mergedLen = alnLen;
+    if (database.trimRequested) alnLen = database.trimmedLen >= 0 ? database.trimmedLen : trimDatabaseRows(&database, &option, alnLen);      // (trim.cpp: in the last download, or on an uploaded copy)
+    io::writeFinalMSA(&database, &option, alnLen);                          // :280: database order -- backbone rows in file order, then the new sequences
     const double t3 = nowMs();
     const size_t levels = progressive::gpu::levelRecords(&database).size();
     std::cerr << "Placed " << (database.sequences.size() - (size_t)groups.backboneRows) << " sequences along the tree into " << groups.backboneRows
-              << " backbone rows in " << sq.groups << " groups: final alignment length " << alnLen << " (backbone " << groups.backboneLen << ")\n";
+              << " backbone rows in " << sq.groups << " groups: final alignment length " << mergedLen << " (backbone " << groups.backboneLen << ")\n";
     if (option.printDetail)
         fprintf(stderr, "Placement-on-tree phases: groups %d, rows %d, columns %lld -> %lld, squeeze kernels %.3f ms (call %.3f ms, row bytes read %lld, written %lld), levels %zu; "
                         "read %.3f ms, align %.3f ms, write %.3f ms\n", sq.groups, sq.rows, (long long)sq.colsBefore, (long long)sq.colsAfter, sq.kernelMs, sq.callMs,

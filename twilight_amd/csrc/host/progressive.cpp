@@ -278,6 +278,7 @@ void msaOnSubtree(Tree *T, SequenceDB *database, Option *option, Params &param, 
         // device-resident mode: the rows come back now, unless nothing on the host needs them yet (library caller without a deferred pass) or the
         // deferred pass runs on the resident rows as well (then they come back after it, below)
         const bool stayResident = database->fallback_nodes.empty() ? database->lazyRows : database->residentDeferred;
+        database->lastDownload = database->fallback_nodes.empty();      // (no deferred pass follows: nothing rewrites rows behind this download)
         if (database->afterMainPass && !stayResident) { database->afterMainPass(T); database->afterMainPass = nullptr; }
     }
     if (database->fallback_nodes.empty()) updateAlignment(T->root, database);
@@ -299,6 +300,7 @@ void msaOnSubtree(Tree *T, SequenceDB *database, Option *option, Params &param, 
     std::cerr << "Realign profiles that have been deferred. Total profiles/sequences: " << database->fallback_nodes.size() << " / " << deferredSeqs << '\n';
     database->fallback_nodes.clear();
     progressiveAlignment(T, database, option, levels, param, deferredKernel);
+    database->lastDownload = true;
     if (database->afterMainPass && !database->lazyRows) { database->afterMainPass(T); database->afterMainPass = nullptr; }
     updateAlignment(T->root, database);
     database->currentTask = 0;

@@ -213,8 +213,15 @@ int runSubtrees(Option &option)
     tot.finish = nowMs() - t;
     t = nowMs();
     std::vector<int32_t> outLen((size_t)nRows);
-    std::vector<char> rows((size_t)nRows * (size_t)W + 1);
-    if ((rc = twl_store_read_rows_of(st, nRows, rowIds.data(), rows.data(), outLen.data())) != TWL_OK) die("twl_store_read_rows_of", rc);
+    std::vector<char> rows;
+    if (option.trimRule >= 0) {            // the rows lose their gappy columns on the device first (trim.cpp): W is the kept length from here on
+        std::vector<const std::string *> nameOf;
+        for (const Subtree &s : subs) for (const std::string &nm : s.names) nameOf.push_back(&nm);
+        W = trimAndReadRows(option, st, nRows, rowIds.data(), [&](int32_t k) { return writtenNameOf(option, *nameOf[(size_t)k]); }, rows);
+    } else {
+        rows.resize((size_t)nRows * (size_t)W + 1);
+        if ((rc = twl_store_read_rows_of(st, nRows, rowIds.data(), rows.data(), outLen.data())) != TWL_OK) die("twl_store_read_rows_of", rc);
+    }
     tot.read = nowMs() - t;
     twl_merge_destroy(mg);
     twl_store_destroy(st);

@@ -112,6 +112,8 @@ using FloatPair = std::pair<float, float>;
 using alnPath = std::vector<int8_t>;
 using Profile = std::vector<std::vector<float>>;
 
+struct SequenceDB;
+
 // reference msa.hpp:55-96; values are the CLI defaults of twilight-main.cpp:13-84
 struct Option {
     int alnMode = DEFAULT_ALN;
@@ -159,6 +161,14 @@ struct Option {
     int directionSeeds = 0;          // --direction-seeds S: the directions are decided against S seed sequences; 0: the smallest S with S * S >= 4 N
     std::string writeDirectionsFile; // --write-directions: one "name<TAB>+|-" line per kept record, in input order
     std::unordered_set<std::string> reversedNames;      // the records of seqFile that adjustDirections found reversed: read reverse-complemented, written as _R_<name>
+    int trimRule = -1;               // the rule by which the written rows lose columns (include/twl_trim.h): 0 --trim-gappy, 1 --trim-to; -1: they are written whole (trim.cpp)
+    double trimGappy = 1.0;          // --trim-gappy T: a column with more than floor(T * N) gaps among the N written rows is left out
+    std::string trimToName;          // --trim-to NAME: the columns in which the written row called NAME holds '-' are left out
+    std::string writeColumnsFile;    // --write-columns: one "new<TAB>old<TAB>gaps" line per kept column
+    // set by the binary that carries the trim (main.cpp): trims the finished host rows of a run of runDefaultAlignment on an uploaded copy, returns the kept length
+    std::function<int(SequenceDB *, Option *, int)> trimHostRows;
+    // ... and on the run's own store (a twl_store *) in front of the last download; sets SequenceDB::trimmedLen, returns what to call once the rows are on the host
+    std::function<std::function<void()>(SequenceDB *, Option *, void *)> trimResidentRows;
     // scoring flags (consumed by Params)
     float match = 18, mismatch = -8, transition = -4, gapOpen = -50, gapExtend = -5, xdrop = 600;
     bool hasGapEnds = false;
@@ -213,6 +223,9 @@ struct SequenceDB {
     std::function<void(Tree *)> afterMainPass;    // set by the device-resident level kernel: bring rows/caches back to the host
     bool residentDeferred = false;                 // ... and that kernel runs the deferred pass on the resident rows too: they come back after it
     bool lazyRows = false;                         // library use (twl_msa.h): leave the rows in HBM after the main pass until somebody needs them
+    bool trimRequested = false;                    // the run's output is trimmed (Option::trimRule): the download that is the run's last may trim the resident rows first
+    bool lastDownload = false;                     // msaOnSubtree sets it in front of that download: no level rewrites rows behind it
+    int trimmedLen = -1;                           // >= 0: that download trimmed the rows on the device; their length from there on
     void addSequence(int id, const std::string &name, std::string &seq, int subtreeIdx, float weight, bool debug);
     bool debug();      // --check: true when every aligned row reproduces its input sequence and all rows are equally long
     ~SequenceDB();
@@ -344,7 +357,13 @@ int runDefaultAlignment(Option &option, alnFunction kernel, alnFunction deferred
 // allowSubtrees: the binary carries the subtree mode too: -m/--max-subtree N with -t, -i, -o sets Option::maxSubtree
 // allowGuide: the binary builds the guide tree itself when none is given: -i and -o without -t, -a or -f sets Option::buildTree
 //             ... and knows --iterations K, --mask-gappy T and --retree-seeds S (retree.cpp); without it all three are unsupported options
-bool parseCommandLine(int argc, char **argv, Option &option, bool allowPlacement = false, bool allowMerge = false, bool allowSubtrees = false, bool allowGuide = false);
+// allowTrim: the binary can write its alignment without the gappy columns: --trim-gappy T, --trim-to NAME and --write-columns FILE (trim.cpp);
+//            without it all three are unsupported options
+bool parseCommandLine(int argc, char **argv, Option &option, bool allowPlacement = false, bool allowMerge = false, bool allowSubtrees = false, bool allowGuide = false,
+                      bool allowTrim = false);
+// --trim-gappy / --trim-to (trim.cpp, libtwl_host.so): gives a run with Option::trimRule its two trim hooks; every mode then writes its rows without
+// the columns the rule leaves out, decided and compacted on the device (include/twl_trim.h).
+void enableTrim(Option &option);
 // The guide tree of a run: from option.treeText when the run built it, from the file option.treeFile otherwise; the same parser either way.
 Tree *openTree(const Option &option);
 // No -t (guide.cpp, libtwl_host.so): the sequences of option.seqFile -> shared k-mer counts of all pairs on the device -> distances -> UPGMA ->

@@ -13,6 +13,7 @@
 #include "../../include/twl_retree.h"
 #include "../../include/twl_retree_set.h"
 #include "../../include/twl_backbone.h"
+#include "../../include/twl_trim.h"
 #include "level_kernels.hip.h"
 #include "restore_kernels.hip.h"
 #include "place_kernels.hip.h"
@@ -23,6 +24,7 @@
 #include "retree_kernels.hip.h"
 #include "retree_stage_kernels.hip.h"
 #include "backbone_kernels.hip.h"
+#include "trim_kernels.hip.h"
 #include "talco_kernel.hip.h"
 #include "talco_nuc.hip.h"
 #include "talco_global.hip.h"
@@ -685,3 +687,4 @@ int twl_mt_tables(int device, twl_mt_dims *dims, int32_t *order, int32_t *anchor
 #include "twl_retree.inc.hip"
 #include "twl_retree_set.inc.hip"
 #include "twl_backbone.inc.hip"
+#include "twl_trim.inc.hip"

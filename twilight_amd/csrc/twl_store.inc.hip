@@ -244,6 +244,9 @@ struct twl_store {
     Buf x_send, x_recv;          // device blocks of the subtree exchange of a sharded run (twl_store_exchange_buffers)
     double prepare_ms = 0, commit_ms = 0;
     double squeeze_ms = 0;       // HIP-event time of the kernels of the last twl_store_squeeze_groups (twl_backbone.inc.hip)
+    Buf trim_gaps, trim_cols;    // of the last twl_store_trim_columns (twl_trim.inc.hip): gaps of its trim_W columns, the trim_kept columns it kept
+    int32_t trim_W = -1, trim_kept = 0;      // trim_W < 0: no trim has run
+    double trim_ms = 0;          // HIP-event time of its kernels
 };
 
 namespace {
@@ -331,7 +334,7 @@ struct StoreEnd {
         (void)hipStreamSynchronize(s->d->stream2);
         s->cache.clear();                                // (the profiles' buffers go back to the device's pool)
         release_level(s->lv);
-        for (Buf *b : {&s->rows[0], &s->rows[1], &s->lut, &s->d_gather, &s->x_send, &s->x_recv}) b->release();
+        for (Buf *b : {&s->rows[0], &s->rows[1], &s->lut, &s->d_gather, &s->x_send, &s->x_recv, &s->trim_gaps, &s->trim_cols}) b->release();
         s->up_rows.release();
         s->d->live_stores -= 1;
     }

@@ -2,6 +2,7 @@
 // single-partition case (no -m), plus the handful of CLI flags the hot path needs (names as in twilight-main.cpp:13-84).
 #include "twl_host.hpp"
 
+#include <unistd.h>
 #include <algorithm>
 #include <chrono>
 #include <climits>
@@ -34,7 +35,8 @@ static bool flag(const char *a, const char *s, const char *l) { return (s && !st
 
 bool parseCommandLine(int argc, char **argv, Option &o, bool allowPlacement, bool allowMerge, bool allowSubtrees, bool allowGuide, bool allowTrim)
 {
-    bool typeGiven = false, subtreesGiven = false, maskGiven = false, trimGappyGiven = false, trimToGiven = false;
+    const bool allowCompare = o.allowCompare;
+    bool typeGiven = false, subtreesGiven = false, maskGiven = false, trimGappyGiven = false, trimToGiven = false, iterationsGiven = false;
     o.cpuNum = 0;
     for (int i = 1; i < argc; ++i) {
         const char *a = argv[i];
@@ -101,6 +103,7 @@ bool parseCommandLine(int argc, char **argv, Option &o, bool allowPlacement, boo
             const long n = strtol(v, &end, 10);
             if (end == v || *end != '\0' || n < 1 || n > 5) { std::cerr << "ERROR: --iterations needs a number of runs from 1 to 5 (got " << v << ").\n"; exit(1); }
             o.iterations = (int)n;
+            iterationsGiven = true;
         }
         else if (allowGuide && flag(a, nullptr, "--mask-gappy")) {
             const char *v = val();
@@ -136,6 +139,9 @@ bool parseCommandLine(int argc, char **argv, Option &o, bool allowPlacement, boo
         }
         else if (allowTrim && flag(a, nullptr, "--trim-to")) { o.trimToName = val(); trimToGiven = true; }
         else if (allowTrim && flag(a, nullptr, "--write-columns")) o.writeColumnsFile = val();
+        else if (allowCompare && flag(a, nullptr, "--compare")) o.compareFile = val();
+        else if (allowCompare && flag(a, nullptr, "--write-compare")) o.writeCompareFile = val();
+        else if (allowCompare && flag(a, nullptr, "--evaluate")) o.evaluateFile = val();
         else if (flag(a, nullptr, "--overwrite")) {}
         else if (flag(a, "-h", "--help")) return false;
         else { std::cerr << "ERROR: unsupported option " << a << " (this build covers the tree+sequences alignment mode only)\n"; exit(1); }
@@ -161,6 +167,26 @@ bool parseCommandLine(int argc, char **argv, Option &o, bool allowPlacement, boo
         if (o.hostStaged) { std::cerr << "ERROR: --host-staged is not available with --trim-gappy or --trim-to (the columns are decided on the device).\n"; exit(1); }
         if (o.gpuIdx.size() > 1 || o.gpuNum > 1) { std::cerr << "ERROR: --trim-gappy and --trim-to run on one GPU: give at most one --gpu-index.\n"; exit(1); }
         o.trimRule = trimToGiven ? 1 : 0;
+    }
+    if (!o.writeCompareFile.empty() && o.compareFile.empty()) { std::cerr << "ERROR: --write-compare applies to a run with --compare: only there is an alignment compared.\n"; exit(1); }
+    if (!o.evaluateFile.empty() && o.compareFile.empty()) { std::cerr << "ERROR: --evaluate needs --compare: the reference alignment the file is compared with.\n"; exit(1); }
+    if (!o.compareFile.empty()) {          // the written alignment compared with a reference alignment (compare.cpp): on one GPU, over the rows as the input holds them
+        if (!o.evaluateFile.empty() && (!o.treeFile.empty() || !o.seqFile.empty() || !o.backboneAlnFile.empty() || !o.msaDir.empty() || !o.outFile.empty() || subtreesGiven || iterationsGiven)) {
+            std::cerr << "ERROR: --evaluate compares two files and runs nothing: it cannot be combined with -t, -i, -a, -f, -o, -m or --iterations.\n"; exit(1);
+        }
+        if (!o.writeCompareFile.empty() && o.writeCompareFile == o.outFile) { std::cerr << "ERROR: --write-compare names the same file as -o.\n"; exit(1); }
+        if (o.adjustDirection) { std::cerr << "ERROR: --compare cannot be combined with --adjust-direction: a turned row does not hold the residues of its reference row.\n"; exit(1); }
+        if (o.keepLength) { std::cerr << "ERROR: --compare cannot be combined with --keep-length: the written rows leave insertions out, so they are not the input's residues.\n"; exit(1); }
+        if (trimGappyGiven || trimToGiven) { std::cerr << "ERROR: --compare cannot be combined with --trim-gappy or --trim-to: the written rows leave columns out, so they are not the input's residues.\n"; exit(1); }
+        if (o.hostStaged) { std::cerr << "ERROR: --host-staged is not available with --compare (the comparison runs on the device).\n"; exit(1); }
+        if (o.gpuIdx.size() > 1 || o.gpuNum > 1) { std::cerr << "ERROR: --compare runs on one GPU: give at most one --gpu-index.\n"; exit(1); }
+        // the last check in front of the run: a mistyped path must not cost the run (nothing is read here)
+        if (!o.evaluateFile.empty() && access(o.evaluateFile.c_str(), R_OK) != 0) { std::cerr << "ERROR: --evaluate: cant open file: " << o.evaluateFile << '\n'; exit(1); }
+        if (access(o.compareFile.c_str(), R_OK) != 0) { std::cerr << "ERROR: --compare: cant open file: " << o.compareFile << '\n'; exit(1); }
+        if (!o.evaluateFile.empty()) {     // nothing else is read or run
+            if (o.gpuIdx.empty() && o.gpuNum > 0) for (int g = 0; g < o.gpuNum; ++g) o.gpuIdx.push_back(g);
+            return true;
+        }
     }
     if (o.adjustDirection) {               // directions (strand.cpp): decided on one GPU before anything else reads -i; the records of -i only
         if (!o.msaDir.empty()) { std::cerr << "ERROR: --adjust-direction cannot be combined with -f: the rows of an alignment cannot be turned.\n"; exit(1); }

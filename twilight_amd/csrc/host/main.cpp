@@ -7,6 +7,7 @@
 //   twilight-mi355x -t tree.nwk -i seqs.fa -o out.aln -m N [...] (built with TWL_SUBTREE: the tree aligned in subtrees of at most N leaves, subtrees.cpp)
 //   twilight-mi355x -i seqs.fa -o out.aln [--write-tree t.nwk] [--tree-seeds S]   (built with TWL_GUIDE: no tree given, the guide tree is built from the sequences, guide.cpp)
 //   twilight-mi355x [-t tree.nwk | -a backbone.aln] -i seqs.fa -o out.aln --adjust-direction [--direction-seeds S] [--write-directions FILE]   (TWL_GUIDE: reverse-complemented records turned first, strand.cpp)
+//   twilight-mi355x <any form that writes -o> --compare ref.aln [--write-compare FILE]; twilight-mi355x --evaluate est.aln --compare ref.aln   (TWL_COMPARE: compare.cpp)
 //   twilight-mi355x [-t tree.nwk] -i seqs.fa -o out.aln --iterations K [--mask-gappy T] [--retree-seeds S]   (TWL_GUIDE: the run K times, the tree rebuilt from every alignment but the last, retree.cpp)
 #include "twl_host.hpp"
 
@@ -80,6 +81,12 @@ int main(int argc, char **argv)
 #else
     const bool trim = false;
 #endif
+#ifdef TWL_COMPARE
+    const bool compare = true;
+#else
+    const bool compare = false;
+#endif
+    option.allowCompare = compare;
     if (!msa::parseCommandLine(argc, argv, option, placement, merging, subtrees, guide, trim)) {
         std::cerr << "usage: twilight-mi355x -t <tree.nwk> -i <sequences.fa[.gz]> -o <out.aln> [-r 0.95] [--type n|p] [--match 18 --mismatch -8 --transition -4\n"
                      "        --gap-open -50 --gap-extend -5 --gap-ends X --xdrop 600] [-w] [--rooted] [--filter] [--check] [-v] [--gpu-index 0,1] [--host-staged]\n";
@@ -108,8 +115,17 @@ int main(int argc, char **argv)
         if (trim) std::cerr << "       every form above but --keep-length: [--trim-gappy T | --trim-to NAME] [--write-columns <file>]   (one GPU, no --host-staged)\n"
                                "        (the alignment is written without its gappy columns: --trim-gappy keeps the columns in which at most floor(T * N) of the N written rows hold '-',\n"
                                "         T in [0, 1]; --trim-to keeps the columns in which the written row called NAME holds a letter; --write-columns lists new<TAB>old<TAB>gaps per kept column)\n";
+        if (compare) std::cerr << "       every form above but --adjust-direction, --keep-length, --trim-gappy, --trim-to: --compare <reference.aln[.gz]> [--write-compare <file>]   (one GPU, no --host-staged)\n"
+                                  "        (the written rows are matched by name with the rows of the reference alignment and compared with them on the device; one line on stderr:\n"
+                                  "         shared residue pairs over the reference's pairs (SP), over the output's pairs (modeler), reference columns recovered whole (TC);\n"
+                                  "         --write-compare lists #key<TAB>value per number of that line, then column<TAB>letters<TAB>pairs<TAB>shared<TAB>distinct<TAB>recovered per written column)\n"
+                                  "       twilight-mi355x --evaluate <alignment.aln[.gz]> --compare <reference.aln[.gz]> [--write-compare <file>] [--gpu-index 0] [-v]   (no run: the two files are compared)\n";
         return 1;
     }
+#ifdef TWL_COMPARE
+    if (!option.evaluateFile.empty()) return msa::runEvaluate(option);
+    msa::enableCompare(option);
+#endif
 #ifdef TWL_TRIM
     msa::enableTrim(option);
 #endif

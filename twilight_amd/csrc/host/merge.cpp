@@ -46,7 +46,7 @@ struct MsaFile { std::string path; std::vector<std::string> names, rows; int32_t
 struct MergeTotals { double count = 0, finish = 0, read = 0, write = 0; progressive::gpu::MergeLevelTotals level; };
 
 // the files' records in order; rows: all rows at W columns back to back, or nullptr for the rows as they were read
-void writeRecords(const std::string &outFile, const std::vector<MsaFile> &files, const char *rows, int32_t W)
+void writeRecords(const Option &option, const std::vector<MsaFile> &files, const char *rows, int32_t W)
 {
     std::vector<const std::string *> names;
     std::vector<const char *> rowAt;
@@ -55,7 +55,7 @@ void writeRecords(const std::string &outFile, const std::vector<MsaFile> &files,
             rowAt.push_back(rows ? rows + names.size() * (size_t)W : f.rows[r].data());
             names.push_back(&f.names[r]);
         }
-    io::writeRecords(outFile, names, rowAt, W);
+    io::writeRecords(option.outFile, names, rowAt, W, &option);      // (no name is ever turned in a merge: --adjust-direction is refused with -f)
 }
 
 }  // namespace
@@ -160,11 +160,11 @@ int runMerge(Option &option)
         for (const std::string &r : files[0].rows) rowPtr.push_back(r.data());
         std::vector<char> rows;
         const int32_t kept = trimHostRows(option, rowPtr, files[0].L, [&](int32_t k) { return files[0].names[(size_t)k]; }, rows);
-        writeRecords(option.outFile, files, rows.data(), kept);
+        writeRecords(option, files, rows.data(), kept);
         return kept;
     }
     if (G == 1) {      // nothing to merge: the file comes back as it is
-        writeRecords(option.outFile, files, nullptr, files[0].L);
+        writeRecords(option, files, nullptr, files[0].L);
         return files[0].L;
     }
 
@@ -237,7 +237,7 @@ int runMerge(Option &option)
     twl_merge_destroy(mg);
     twl_store_destroy(st);
     t = nowMs();
-    writeRecords(option.outFile, files, rows.data(), W);
+    writeRecords(option, files, rows.data(), W);
     tot.write = nowMs() - t;
     std::cerr << "Merged " << G << " alignments (" << nRows << " rows): final alignment length " << W << ", " << tot.level.run.retries << " retried DP run(s)\n";
     if (option.printDetail)

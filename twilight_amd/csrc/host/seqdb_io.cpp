@@ -482,10 +482,18 @@ static void writeRow(std::ostream &out, const std::string &name, const char *row
 
 void writeAlignment(const std::string &fileName, SequenceDB *database, int alnLen, const Option *option)     // io.cpp:512-525 (plain FASTA, input order)
 {
-    std::ofstream out(fileName, std::ios::binary);
-    if (!out) { fprintf(stderr, "ERROR: Failed to open file: %s\n", fileName.c_str()); exit(1); }
-    for (auto *s : database->sequences)
-        if (!s->lowQuality) writeRow(out, s->name, &s->alnStorage[s->storage][0], alnLen, option && option->reversedNames.count(s->name));
+    {
+        std::ofstream out(fileName, std::ios::binary);
+        if (!out) { fprintf(stderr, "ERROR: Failed to open file: %s\n", fileName.c_str()); exit(1); }
+        for (auto *s : database->sequences)
+            if (!s->lowQuality) writeRow(out, s->name, &s->alnStorage[s->storage][0], alnLen, option && option->reversedNames.count(s->name));
+    }
+    if (option && option->compareWritten && fileName == option->outFile) {      // --compare (compare.cpp): the file is closed, the records as they were written
+        std::vector<std::string> names;
+        std::vector<const char *> rows;
+        for (auto *s : database->sequences) if (!s->lowQuality) { names.push_back(s->name); rows.push_back(&s->alnStorage[s->storage][0]); }
+        option->compareWritten(names, rows, alnLen);
+    }
 }
 
 void writeRecords(const std::string &fileName, const std::vector<const std::string *> &names, const std::vector<const char *> &rows, int W, const Option *option,
@@ -494,7 +502,13 @@ void writeRecords(const std::string &fileName, const std::vector<const std::stri
     std::ofstream out(fileName, std::ios::binary);
     if (!out) { fprintf(stderr, "ERROR: Failed to open file: %s\n", fileName.c_str()); exit(1); }
     for (size_t k = 0; k < names.size(); ++k) writeRow(out, *names[k], rows[k], W, option && k >= firstRenamable && option->reversedNames.count(*names[k]));
+    out.close();
     if (!out) { fprintf(stderr, "ERROR: Failed to write file: %s\n", fileName.c_str()); exit(1); }
+    if (option && option->compareWritten && fileName == option->outFile) {      // --compare (compare.cpp): the file is closed, the records as they were written
+        std::vector<std::string> written;
+        for (const std::string *n : names) written.push_back(*n);
+        option->compareWritten(written, rows, W);
+    }
 }
 
 void writeFinalMSA(SequenceDB *database, Option *option, int alnLen)                  // io.cpp:465-488, DEFAULT_ALN branch

@@ -165,6 +165,12 @@ struct Option {
     double trimGappy = 1.0;          // --trim-gappy T: a column with more than floor(T * N) gaps among the N written rows is left out
     std::string trimToName;          // --trim-to NAME: the columns in which the written row called NAME holds '-' are left out
     std::string writeColumnsFile;    // --write-columns: one "new<TAB>old<TAB>gaps" line per kept column
+    bool allowCompare = false;       // set by the binary that carries the comparison (main.cpp) before it parses: --compare, --write-compare and --evaluate are options
+    std::string compareFile;         // --compare REF: the written alignment is compared with this reference alignment (compare.cpp)
+    std::string writeCompareFile;    // --write-compare: "#key<TAB>value" lines of the totals, then one line per written column
+    std::string evaluateFile;        // --evaluate EST: no run, EST is compared with compareFile
+    // set by the binary that carries the comparison (main.cpp): called by the writers of -o once the file is closed, with the records as they were written
+    std::function<void(const std::vector<std::string> &, const std::vector<const char *> &, int)> compareWritten;
     // set by the binary that carries the trim (main.cpp): trims the finished host rows of a run of runDefaultAlignment on an uploaded copy, returns the kept length
     std::function<int(SequenceDB *, Option *, int)> trimHostRows;
     // ... and on the run's own store (a twl_store *) in front of the last download; sets SequenceDB::trimmedLen, returns what to call once the rows are on the host
@@ -361,6 +367,13 @@ int runDefaultAlignment(Option &option, alnFunction kernel, alnFunction deferred
 //            without it all three are unsupported options
 bool parseCommandLine(int argc, char **argv, Option &option, bool allowPlacement = false, bool allowMerge = false, bool allowSubtrees = false, bool allowGuide = false,
                       bool allowTrim = false);
+// Option::allowCompare, set before the call: the binary can compare what it writes with a reference alignment: --compare REF, --write-compare FILE,
+// --evaluate EST (compare.cpp); without it all three are unsupported options
+// --compare (compare.cpp, libtwl_host.so): gives a run with Option::compareFile its hook behind the writers (seqdb_io.cpp); the rows as they were
+// written are matched with the reference's rows by name and compared on the device (include/twl_compare.h).
+void enableCompare(Option &option);
+// --evaluate EST --compare REF: no run, the two files compared.  Returns the process's exit code.
+int runEvaluate(Option &option);
 // --trim-gappy / --trim-to (trim.cpp, libtwl_host.so): gives a run with Option::trimRule its two trim hooks; every mode then writes its rows without
 // the columns the rule leaves out, decided and compacted on the device (include/twl_trim.h).
 void enableTrim(Option &option);

@@ -142,6 +142,9 @@ bool parseCommandLine(int argc, char **argv, Option &o, bool allowPlacement, boo
         else if (allowCompare && flag(a, nullptr, "--compare")) o.compareFile = val();
         else if (allowCompare && flag(a, nullptr, "--write-compare")) o.writeCompareFile = val();
         else if (allowCompare && flag(a, nullptr, "--evaluate")) o.evaluateFile = val();
+        else if (o.allowScore && flag(a, nullptr, "--score")) o.score = true;
+        else if (o.allowScore && flag(a, nullptr, "--write-score")) o.writeScoreFile = val();
+        else if (o.allowScore && flag(a, nullptr, "--score-alignment")) o.scoreAlignmentFile = val();
         else if (flag(a, nullptr, "--overwrite")) {}
         else if (flag(a, "-h", "--help")) return false;
         else { std::cerr << "ERROR: unsupported option " << a << " (this build covers the tree+sequences alignment mode only)\n"; exit(1); }
@@ -167,6 +170,27 @@ bool parseCommandLine(int argc, char **argv, Option &o, bool allowPlacement, boo
         if (o.hostStaged) { std::cerr << "ERROR: --host-staged is not available with --trim-gappy or --trim-to (the columns are decided on the device).\n"; exit(1); }
         if (o.gpuIdx.size() > 1 || o.gpuNum > 1) { std::cerr << "ERROR: --trim-gappy and --trim-to run on one GPU: give at most one --gpu-index.\n"; exit(1); }
         o.trimRule = trimToGiven ? 1 : 0;
+    }
+    if (!o.writeScoreFile.empty() && !o.score && o.scoreAlignmentFile.empty()) { std::cerr << "ERROR: --write-score applies to a run with --score or --score-alignment: only there is an alignment scored.\n"; exit(1); }
+    if (!o.writeScoreFile.empty() && o.writeScoreFile == o.outFile) { std::cerr << "ERROR: --write-score names the same file as -o.\n"; exit(1); }
+    if (!o.scoreAlignmentFile.empty()) {   // a file scored (score.cpp): nothing is run
+        if (!o.treeFile.empty() || !o.seqFile.empty() || !o.backboneAlnFile.empty() || !o.msaDir.empty() || !o.outFile.empty() || subtreesGiven || iterationsGiven || !o.evaluateFile.empty()) {
+            std::cerr << "ERROR: --score-alignment scores a file and runs nothing: it cannot be combined with -t, -i, -a, -f, -o, -m, --iterations or --evaluate.\n"; exit(1);
+        }
+        if (o.score) { std::cerr << "ERROR: --score-alignment cannot be combined with --score: --score applies to the alignment a run writes.\n"; exit(1); }
+        if (o.hostStaged) { std::cerr << "ERROR: --host-staged is not available with --score-alignment (the score's integers are counted on the device).\n"; exit(1); }
+        if (o.gpuIdx.size() > 1 || o.gpuNum > 1) { std::cerr << "ERROR: --score-alignment runs on one GPU: give at most one --gpu-index.\n"; exit(1); }
+        if (access(o.scoreAlignmentFile.c_str(), R_OK) != 0) { std::cerr << "ERROR: --score-alignment: cant open file: " << o.scoreAlignmentFile << '\n'; exit(1); }
+        if (o.gpuIdx.empty() && o.gpuNum > 0) for (int g = 0; g < o.gpuNum; ++g) o.gpuIdx.push_back(g);
+        o.typeGiven = typeGiven;
+        if (!typeGiven) o.type = io::detectType(o.scoreAlignmentFile);
+        return true;
+    }
+    if (o.score) {                         // the written alignment scored (score.cpp): on one GPU, over the rows as they are written
+        if (o.keepLength) { std::cerr << "ERROR: --score cannot be combined with --keep-length: the written rows leave insertions out, so the score would not be that of the sequences.\n"; exit(1); }
+        if (trimGappyGiven || trimToGiven) { std::cerr << "ERROR: --score cannot be combined with --trim-gappy or --trim-to: the written rows leave columns out, so the score would not be that of the alignment.\n"; exit(1); }
+        if (o.hostStaged) { std::cerr << "ERROR: --host-staged is not available with --score (the score's integers are counted on the device).\n"; exit(1); }
+        if (o.gpuIdx.size() > 1 || o.gpuNum > 1) { std::cerr << "ERROR: --score runs on one GPU: give at most one --gpu-index.\n"; exit(1); }
     }
     if (!o.writeCompareFile.empty() && o.compareFile.empty()) { std::cerr << "ERROR: --write-compare applies to a run with --compare: only there is an alignment compared.\n"; exit(1); }
     if (!o.evaluateFile.empty() && o.compareFile.empty()) { std::cerr << "ERROR: --evaluate needs --compare: the reference alignment the file is compared with.\n"; exit(1); }

@@ -8,6 +8,7 @@
 //   twilight-mi355x -i seqs.fa -o out.aln [--write-tree t.nwk] [--tree-seeds S]   (built with TWL_GUIDE: no tree given, the guide tree is built from the sequences, guide.cpp)
 //   twilight-mi355x [-t tree.nwk | -a backbone.aln] -i seqs.fa -o out.aln --adjust-direction [--direction-seeds S] [--write-directions FILE]   (TWL_GUIDE: reverse-complemented records turned first, strand.cpp)
 //   twilight-mi355x <any form that writes -o> --compare ref.aln [--write-compare FILE]; twilight-mi355x --evaluate est.aln --compare ref.aln   (TWL_COMPARE: compare.cpp)
+//   twilight-mi355x <any form that writes -o> --score [--write-score FILE]; twilight-mi355x --score-alignment est.aln   (TWL_SCORE: score.cpp)
 //   twilight-mi355x [-t tree.nwk] -i seqs.fa -o out.aln --iterations K [--mask-gappy T] [--retree-seeds S]   (TWL_GUIDE: the run K times, the tree rebuilt from every alignment but the last, retree.cpp)
 #include "twl_host.hpp"
 
@@ -87,6 +88,12 @@ int main(int argc, char **argv)
     const bool compare = false;
 #endif
     option.allowCompare = compare;
+#ifdef TWL_SCORE
+    const bool score = true;
+#else
+    const bool score = false;
+#endif
+    option.allowScore = score;
     if (!msa::parseCommandLine(argc, argv, option, placement, merging, subtrees, guide, trim)) {
         std::cerr << "usage: twilight-mi355x -t <tree.nwk> -i <sequences.fa[.gz]> -o <out.aln> [-r 0.95] [--type n|p] [--match 18 --mismatch -8 --transition -4\n"
                      "        --gap-open -50 --gap-extend -5 --gap-ends X --xdrop 600] [-w] [--rooted] [--filter] [--check] [-v] [--gpu-index 0,1] [--host-staged]\n";
@@ -120,8 +127,17 @@ int main(int argc, char **argv)
                                   "         shared residue pairs over the reference's pairs (SP), over the output's pairs (modeler), reference columns recovered whole (TC);\n"
                                   "         --write-compare lists #key<TAB>value per number of that line, then column<TAB>letters<TAB>pairs<TAB>shared<TAB>distinct<TAB>recovered per written column)\n"
                                   "       twilight-mi355x --evaluate <alignment.aln[.gz]> --compare <reference.aln[.gz]> [--write-compare <file>] [--gpu-index 0] [-v]   (no run: the two files are compared)\n";
+        if (score) std::cerr << "       every form above but --keep-length, --trim-gappy, --trim-to: --score [--write-score <file>]   (one GPU, no --host-staged)\n"
+                                "        (the affine sum-of-pairs score of the written rows under the run's own substitution scores and gap penalties, counted on the device in exact integers; one line on stderr:\n"
+                                "         score: rows N columns W pairs P letters L gapcols G runs R terminal RT/GT score S per_pair S/P; a pair with a letter outside the alphabet scores 0, with -w too;\n"
+                                "         with --iterations one line per run, prefixed run k; --write-score lists #key<TAB>value per number and per sub[a][b], then name<TAB>letters<TAB>runs per written row)\n"
+                                "       twilight-mi355x --score-alignment <alignment.aln[.gz]> [--type n|p] [scoring flags] [--write-score <file>] [--gpu-index 0] [-v]   (no run: the file is scored)\n";
         return 1;
     }
+#ifdef TWL_SCORE
+    if (!option.scoreAlignmentFile.empty()) return msa::runScoreAlignment(option);
+    msa::enableScore(option);
+#endif
 #ifdef TWL_COMPARE
     if (!option.evaluateFile.empty()) return msa::runEvaluate(option);
     msa::enableCompare(option);

@@ -200,6 +200,7 @@ int runIterations(Option &option)
     for (int k = 1; k <= option.iterations; ++k) {
         const bool last = k == option.iterations;
         std::cerr << "===== Iteration " << k << " of " << option.iterations << " =====\n";
+        option.scoreRun = k;
         if (last && !treeFile.empty()) {
             std::ofstream out(treeFile, std::ios::binary);
             out << option.treeText;
@@ -208,6 +209,7 @@ int runIterations(Option &option)
         std::string next;
         alnLen = runDefaultAlignment(option, kernel, kernel, last, [&](SequenceDB *db) {
             if (last) return;
+            if (option.scoreWritten) option.scoreWritten(names, finishedRows(db, names, k), db->finalAlnLen);      // --score: a line per run (the last run's comes from its writer)
             progressive::gpu::ensureInit(&option);
             const int device = progressive::gpu::selectedDevices().empty() ? 0 : progressive::gpu::selectedDevices()[0];
             next = option.retreeSeeds > 0 ? rebuildStagedTree(option, db, names, k, device) : rebuildTree(option, db, names, k, device);

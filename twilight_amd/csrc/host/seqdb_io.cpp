@@ -494,6 +494,12 @@ void writeAlignment(const std::string &fileName, SequenceDB *database, int alnLe
         for (auto *s : database->sequences) if (!s->lowQuality) { names.push_back(s->name); rows.push_back(&s->alnStorage[s->storage][0]); }
         option->compareWritten(names, rows, alnLen);
     }
+    if (option && option->scoreWritten && fileName == option->outFile) {        // --score (score.cpp): the same records
+        std::vector<std::string> names;
+        std::vector<const char *> rows;
+        for (auto *s : database->sequences) if (!s->lowQuality) { names.push_back(s->name); rows.push_back(&s->alnStorage[s->storage][0]); }
+        option->scoreWritten(names, rows, alnLen);
+    }
 }
 
 void writeRecords(const std::string &fileName, const std::vector<const std::string *> &names, const std::vector<const char *> &rows, int W, const Option *option,
@@ -508,6 +514,11 @@ void writeRecords(const std::string &fileName, const std::vector<const std::stri
         std::vector<std::string> written;
         for (const std::string *n : names) written.push_back(*n);
         option->compareWritten(written, rows, W);
+    }
+    if (option && option->scoreWritten && fileName == option->outFile) {        // --score (score.cpp): the same records
+        std::vector<std::string> written;
+        for (const std::string *n : names) written.push_back(*n);
+        option->scoreWritten(written, rows, W);
     }
 }
 

@@ -171,6 +171,14 @@ struct Option {
     std::string evaluateFile;        // --evaluate EST: no run, EST is compared with compareFile
     // set by the binary that carries the comparison (main.cpp): called by the writers of -o once the file is closed, with the records as they were written
     std::function<void(const std::vector<std::string> &, const std::vector<const char *> &, int)> compareWritten;
+    bool allowScore = false;         // set by the binary that carries the score (main.cpp) before it parses: --score, --write-score and --score-alignment are options
+    bool score = false;              // --score: the written alignment's affine sum-of-pairs score, one line on stderr (score.cpp)
+    std::string writeScoreFile;      // --write-score: "#key<TAB>value" lines of the numbers, then name<TAB>letters<TAB>runs per written row
+    std::string scoreAlignmentFile;  // --score-alignment FILE: no run, FILE is scored
+    int scoreRun = 0;                // > 0: run k of --iterations, the prefix of the score line (retree.cpp)
+    // set by the binary that carries the score (main.cpp): called by the writers of -o once the file is closed (behind compareWritten), and by --iterations
+    // with the finished rows of every run but the last
+    std::function<void(const std::vector<std::string> &, const std::vector<const char *> &, int)> scoreWritten;
     // set by the binary that carries the trim (main.cpp): trims the finished host rows of a run of runDefaultAlignment on an uploaded copy, returns the kept length
     std::function<int(SequenceDB *, Option *, int)> trimHostRows;
     // ... and on the run's own store (a twl_store *) in front of the last download; sets SequenceDB::trimmedLen, returns what to call once the rows are on the host
@@ -374,6 +382,13 @@ bool parseCommandLine(int argc, char **argv, Option &option, bool allowPlacement
 void enableCompare(Option &option);
 // --evaluate EST --compare REF: no run, the two files compared.  Returns the process's exit code.
 int runEvaluate(Option &option);
+// Option::allowScore, set before the call: the binary can score what it writes: --score, --write-score FILE, --score-alignment FILE (score.cpp);
+// without it all three are unsupported options.
+// --score (score.cpp, libtwl_host.so): gives a run with Option::score its hook behind the writers (seqdb_io.cpp); the rows as they were written go
+// into a store and twl_store_score_rows (include/twl_score.h) counts the integers the score is computed from.
+void enableScore(Option &option);
+// --score-alignment FILE: no run, the file scored.  Returns the process's exit code.
+int runScoreAlignment(Option &option);
 // --trim-gappy / --trim-to (trim.cpp, libtwl_host.so): gives a run with Option::trimRule its two trim hooks; every mode then writes its rows without
 // the columns the rule leaves out, decided and compacted on the device (include/twl_trim.h).
 void enableTrim(Option &option);

@@ -15,6 +15,7 @@
 #include "../../include/twl_backbone.h"
 #include "../../include/twl_trim.h"
 #include "../../include/twl_compare.h"
+#include "../../include/twl_score.h"
 #include "level_kernels.hip.h"
 #include "restore_kernels.hip.h"
 #include "place_kernels.hip.h"
@@ -27,6 +28,7 @@
 #include "backbone_kernels.hip.h"
 #include "trim_kernels.hip.h"
 #include "compare_kernels.hip.h"
+#include "score_kernels.hip.h"
 #include "talco_kernel.hip.h"
 #include "talco_nuc.hip.h"
 #include "talco_global.hip.h"
@@ -691,3 +693,4 @@ int twl_mt_tables(int device, twl_mt_dims *dims, int32_t *order, int32_t *anchor
 #include "twl_backbone.inc.hip"
 #include "twl_trim.inc.hip"
 #include "twl_compare.inc.hip"
+#include "twl_score.inc.hip"

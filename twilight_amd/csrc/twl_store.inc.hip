@@ -247,6 +247,7 @@ struct twl_store {
     Buf trim_gaps, trim_cols;    // of the last twl_store_trim_columns (twl_trim.inc.hip): gaps of its trim_W columns, the trim_kept columns it kept
     int32_t trim_W = -1, trim_kept = 0;      // trim_W < 0: no trim has run
     double trim_ms = 0;          // HIP-event time of its kernels
+    double score_ms[3] = {0, 0, 0};      // of the last twl_store_score_rows (twl_score.inc.hip): pack, column and pair kernels, HIP-event times
 };
 
 namespace {

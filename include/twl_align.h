@@ -171,6 +171,19 @@ typedef struct twl_mt_dims {
 } twl_mt_dims;
 int twl_mt_tables(int device, twl_mt_dims *dims, int32_t *order, int32_t *anchor, int32_t *spath, int32_t *chain, int32_t *rec, int8_t *seg, int32_t *front);
 
+/* Diagnostics: the precomputed column scores (matrix mode 4, score_matrix_kernel) of ONE pair of the LAST twl_align_batch / twl_align_batch_device call on `device`, as
+   that call's first launch read them.  Read-only like twl_mt_tables: the call takes the device's lock, waits for the device's stream and copies; it launches no kernel
+   and changes no knob.  out holds (R + Q) rows of pitch = (Q + 63) & ~63 floats, out[K * pitch + I] = the score of query row I against reference column K - I (K: the
+   anti-diagonal); with dims.corridor > 0 the 64 x 64 tiles further than that many rows from the straight line between the corners hold a quiet NaN.  Floats that belong to
+   no cell (I >= Q, K - I outside [0, R)) are whatever the buffer held.  `out` may be NULL (only `dims` is filled in: a first call tells the size).
+   Returns TWL_ERR_UNSUPPORTED when the last call's first launch did not run on precomputed scores (twl_column_scores, which uses the same buffer, counts as such a call)
+   or when `pair` did not run in it (a side of length 0). */
+typedef struct twl_score_dims {
+    int32_t R, Q, pitch, corridor;               /* the pair's lengths, floats per row of `out`, the corridor the scores were computed in (0: the whole matrix) */
+    int32_t reserved[4];
+} twl_score_dims;
+int twl_dp_score_matrix(int device, int32_t pair, twl_score_dims *dims, float *out);
+
 /* ---- RCCL from the library's own C++ (pairs of a level sharded over the GPUs of a node, one process per GPU) ----
    The collective of a sharded run is ONE all-gather of equal byte blocks per guide-tree level, HBM to HBM over xGMI, on the library's stream of
    `device`.  librccl is loaded at run time (dlopen "librccl.so.1"; a copy already in the process, e.g. PyTorch's, is reused), so the library

@@ -78,6 +78,14 @@ float twlo_column_score(const twlo_params *p, const float *r, const float *q, fl
     return numerator / denom;   /* :444 */
 }
 
+/* twlo_column_score of every query row against every reference column: out[i * R + j] (test aid: one call instead of Q x R) */
+void twlo_column_score_grid(const twlo_params *p, const float *ref, int32_t R, const float *qry, int32_t Q, float denom, float *out)
+{
+    for (int32_t i = 0; i < Q; ++i)
+        for (int32_t j = 0; j < R; ++j)
+            out[(size_t)i * (size_t)R + (size_t)j] = twlo_column_score(p, ref + (size_t)p->P * (size_t)j, qry + (size_t)p->P * (size_t)i, denom);
+}
+
 /* ---- Reduction_tree: TALCO-XDrop.cpp:110-119 ------------------------------------------------ */
 static int32_t uniform_or_minus1(const int32_t *C, int32_t start, int32_t length)
 {

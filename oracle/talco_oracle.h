@@ -117,6 +117,8 @@ int twlo_align_batch(const twlo_params *p, int32_t n_pairs, int32_t seq_len,
 
 /* Score of one column pair, exactly as TALCO-XDrop.cpp:373-444 (before adding S). */
 float twlo_column_score(const twlo_params *p, const float *ref_col, const float *qry_col, float denom);
+/* ... of every query row i against every reference column j of ref[R][P], qry[Q][P]: out[i * R + j], each by twlo_column_score. */
+void twlo_column_score_grid(const twlo_params *p, const float *ref, int32_t R, const float *qry, int32_t Q, float denom, float *out);
 
 #ifdef __cplusplus
 }

@@ -67,6 +67,7 @@ int twl_get_pair_cells(int, uint64_t *, int32_t) { return TWL_ERR_UNSUPPORTED; }
 int twl_column_scores(const twl_params *, int32_t, const float *, const int32_t *, const int32_t *, float *) { return TWL_ERR_UNSUPPORTED; }
 int twl_dp_column_scores(const twl_params *, int32_t, const float *, const float *, const float *, const int32_t *, const int32_t *, float *) { return TWL_ERR_UNSUPPORTED; }
 int twl_mt_tables(int, twl_mt_dims *, int32_t *, int32_t *, int32_t *, int32_t *, int32_t *, int8_t *, int32_t *) { return TWL_ERR_UNSUPPORTED; }
+int twl_dp_score_matrix(int, int32_t, twl_score_dims *, float *) { return TWL_ERR_UNSUPPORTED; }
 
 int twl_store_create(int, char, int32_t, const char *const *, const int32_t *, twl_store **) { return TWL_ERR_UNSUPPORTED; }
 void twl_store_destroy(twl_store *) {}

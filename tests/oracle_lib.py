@@ -41,6 +41,7 @@ def lib():
         _LIB.twlo_align_pair_exits.restype = C.c_int
         _LIB.twlo_tile_from.restype = C.c_int
         _LIB.twlo_column_score.restype = C.c_float
+        _LIB.twlo_column_score_grid.restype = None
     return _LIB
 
 
@@ -163,6 +164,16 @@ def column_score(params: Params, r, q, denom):
     r = np.ascontiguousarray(r, dtype=np.float32)
     q = np.ascontiguousarray(q, dtype=np.float32)
     return float(lib().twlo_column_score(C.byref(params), _fp(r), _fp(q), C.c_float(denom)))
+
+
+def column_score_grid(params: Params, ref, qry, denom) -> np.ndarray:
+    """twlo_column_score of every query row against every reference column: [Q][R] float32, each cell one call of the function above inside the library."""
+    ref = np.ascontiguousarray(ref, dtype=np.float32)
+    qry = np.ascontiguousarray(qry, dtype=np.float32)
+    assert ref.shape[1] == params.P and qry.shape[1] == params.P
+    out = np.zeros((qry.shape[0], ref.shape[0]), dtype=np.float32)
+    lib().twlo_column_score_grid(C.byref(params), _fp(ref), C.c_int32(ref.shape[0]), _fp(qry), C.c_int32(qry.shape[0]), C.c_float(denom), _fp(out))
+    return out
 
 
 _FLIB = None

@@ -55,6 +55,10 @@ def test_struct_layouts_match_header(built):
     # twl_params: int32 + 441 floats + 4 floats + 3 int32; twl_stats: 2 u64 + 3 double + 10 int32
     assert C.sizeof(twl.TwlParams) == 4 + 441 * 4 + 4 * 4 + 3 * 4
     assert C.sizeof(twl.TwlStats) == 2 * 8 + 3 * 8 + 10 * 4 + 160
+    # twl_score_dims (twl_dp_score_matrix): R, Q, pitch, corridor + 4 reserved
+    from twilight_amd import api
+
+    assert C.sizeof(api.TwlScoreDims) == 8 * 4 and [n for n, _ in api.TwlScoreDims._fields_[:4]] == ["R", "Q", "pitch", "corridor"]
 
 
 def test_calls_fail_loudly_without_init_or_gpu(built):
@@ -71,6 +75,11 @@ def test_calls_fail_loudly_without_init_or_gpu(built):
         pytest.skip("library already initialised in this process")
     assert rc == -1
     assert b"twl_init" in lib.twl_last_error()
+    # the read-only diagnostics entries too: an error code, nothing copied
+    from twilight_amd import api
+
+    dm = api.TwlScoreDims()
+    assert lib.twl_dp_score_matrix(C.c_int(0), C.c_int32(0), C.byref(dm), None) == -1 and (dm.R, dm.Q, dm.pitch, dm.corridor) == (0, 0, 0, 0)
     import torch
 
     if not torch.cuda.is_available():

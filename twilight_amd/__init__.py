@@ -14,6 +14,7 @@ from .api import (  # noqa: F401
     align_batch_device,
     column_scores,
     dp_column_scores,
+    dp_score_matrix,
     exported_symbols,
     get_pair_cells,
     get_stats,

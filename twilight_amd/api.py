@@ -41,10 +41,16 @@ class TwlMtDims(C.Structure):
 MT_REC_WORDS = 12      # TWL_MT_REC_WORDS
 
 
+class TwlScoreDims(C.Structure):
+    """twl_score_dims -- one pair's block of the precomputed column scores (include/twl_align.h, twl_dp_score_matrix)."""
+    _fields_ = [(n, C.c_int32) for n in ("R", "Q", "pitch", "corridor")] + [("reserved", C.c_int32 * 4)]
+
+
 _SYMBOLS = ["twl_init", "twl_shutdown", "twl_last_error", "twl_version", "twl_align_batch", "twl_align_batch_device",
             "twl_get_stats", "twl_get_pair_cells", "twl_column_scores", "twl_dp_column_scores", "twl_host_alloc", "twl_host_free", "twl_set_knob",
             "twl_copy_to_device", "twl_copy_from_device", "twl_copy_rows_from_device",
-            "twl_comm_unique_id", "twl_comm_init", "twl_comm_all_gather", "twl_comm_all_gather_host", "twl_comm_destroy", "twl_plan_describe", "twl_mt_tables"]
+            "twl_comm_unique_id", "twl_comm_init", "twl_comm_all_gather", "twl_comm_all_gather_host", "twl_comm_destroy", "twl_plan_describe", "twl_mt_tables",
+            "twl_dp_score_matrix"]
 
 
 def exported_symbols():
@@ -76,6 +82,7 @@ def load_library():
         lib.twl_shutdown.restype = None
         lib.twl_set_knob.restype = C.c_int
         lib.twl_mt_tables.restype = C.c_int
+        lib.twl_dp_score_matrix.restype = C.c_int
         _lib = lib
     return _lib
 
@@ -263,3 +270,17 @@ def mt_tables(device=0) -> dict:
     assert (dm.n_run, dm.slots) == (n, s), "another level ran between the two reads"
     dims = {k: int(getattr(dm, k)) for k, _ in TwlMtDims._fields_ if k != "reserved"}
     return {"dims": dims, "order": order, "anchor": anchor, "spath": spath, "chain": chain, "rec": rec, "seg": seg, "front": front}
+
+
+def dp_score_matrix(pair: int, device=0):
+    """twl_dp_score_matrix: (scores, corridor) of pair `pair` of the last align_batch on `device` whose first launch ran on precomputed scores -- scores[K][I] of
+    shape [R + Q][(Q + 63) & ~63], K the anti-diagonal and I the query row, NaN in the tiles outside the corridor (0: the whole matrix).  Read-only, launches
+    nothing; TwlError when that call did not precompute or the pair did not run."""
+    lib = load_library()
+    dm = TwlScoreDims()
+    _check(lib.twl_dp_score_matrix(C.c_int(device), C.c_int32(pair), C.byref(dm), None))
+    out = np.zeros((dm.R + dm.Q, dm.pitch), dtype=np.float32)
+    d2 = TwlScoreDims()
+    _check(lib.twl_dp_score_matrix(C.c_int(device), C.c_int32(pair), C.byref(d2), _ptr(out, C.c_float)))
+    assert (d2.R, d2.Q, d2.pitch, d2.corridor) == (dm.R, dm.Q, dm.pitch, dm.corridor), "another call ran between the two reads"
+    return out, int(dm.corridor)

@@ -134,6 +134,9 @@ struct Device {
     Buf cols, tb, cells, queue, items, errs, dbg;
     Buf gtb;                                                                     // scratch of the global-memory kernel (DP rows + pointer bytes of its pairs): its own buffer, handed back after the stage when large
     Buf sim, sim_off, blk_off, m24;                                              // precomputed protein scores (matrix mode 4)
+    std::vector<long long> sim_last_off;                                         // twl_dp_score_matrix: per pair of the last call that precomputed, the first float of its block in `sim` (-1: the pair did not run) ...
+    std::vector<int32_t> sim_last_len;                                           // ... its {R, Q} ...
+    int sim_last_corridor = 0;                                                   // ... and the corridor score_matrix_kernel was given.  Empty vectors: the last call did not precompute
     Buf team;                                                                    // mailboxes of the speculative tile start
     Buf mt_chain, mt_rec, mt_seg, mt_spath, mt_stat, mt_jobs, mt_anchor;                    // tile-parallel alignment (talco_nuc.hip.h, MT kernels)
     Buf simdump;                                                                 // twl_dp_column_scores: [Q][R] scores written by the DUMP kernels
@@ -468,6 +471,7 @@ int twl_column_scores(const twl_params *p, int32_t seq_len, const float *freq, c
     if ((rc = d->h2d_len.ensure(2 * sizeof(int32_t)))) return rc;
     if ((rc = d->h2d_num.ensure(2 * sizeof(int32_t)))) return rc;
     if ((rc = d->items.ensure(sizeof(int32_t)))) return rc;
+    d->sim_last_off.clear(); d->sim_last_len.clear(); d->sim_last_corridor = 0;      // (the buffer twl_dp_score_matrix reads is overwritten here)
     if ((rc = d->sim.ensure(simFloats * sizeof(float)))) return rc;
     if ((rc = d->sim_off.ensure(sizeof(long long)))) return rc;
     if ((rc = d->blk_off.ensure(2 * sizeof(int32_t)))) return rc;
@@ -674,6 +678,28 @@ int twl_mt_tables(int device, twl_mt_dims *dims, int32_t *order, int32_t *anchor
     if (rc) return rc;
     std::lock_guard<std::mutex> lk(d->mu);
     return read_mt_tables(d, dims, order, anchor, spath, chain, rec, seg, front);
+}
+
+// twl_dp_score_matrix: a plain copy of one pair's block of the scores score_matrix_kernel left behind, after the device's stream has drained.  No launch.
+int twl_dp_score_matrix(int device, int32_t pair, twl_score_dims *dims, float *out)
+{
+    if (!g_init) { g_err = "twl_init not called"; return TWL_ERR_NOT_INITIALIZED; }
+    Device *d = nullptr;
+    int rc = find_dev(device, &d);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(d->mu);
+    if (d->sim_last_off.empty()) { g_err = "the last call on this device did not precompute its column scores"; return TWL_ERR_UNSUPPORTED; }
+    if (pair < 0 || (size_t)pair >= d->sim_last_off.size()) { g_err = "bad argument"; return TWL_ERR_BAD_ARGUMENT; }
+    if (d->sim_last_off[(size_t)pair] < 0) { g_err = "the pair did not run in the last call"; return TWL_ERR_UNSUPPORTED; }
+    const int32_t R = d->sim_last_len[2 * (size_t)pair], Q = d->sim_last_len[2 * (size_t)pair + 1];
+    const size_t pitch = ((size_t)Q + 63) & ~(size_t)63, floats = (size_t)(R + Q) * pitch;
+    if (dims) { *dims = twl_score_dims{}; dims->R = R; dims->Q = Q; dims->pitch = (int32_t)pitch; dims->corridor = d->sim_last_corridor; }
+    if (!out) return TWL_OK;
+    if (((size_t)d->sim_last_off[(size_t)pair] + floats) * sizeof(float) > d->sim.cap) { g_err = "internal: the pair's block lies outside the score buffer"; return TWL_ERR_HIP; }
+    HIP_TRY(hipSetDevice(d->id));
+    HIP_TRY(hipStreamSynchronize(d->stream));
+    HIP_TRY(hipMemcpy(out, (const float *)d->sim.p + d->sim_last_off[(size_t)pair], floats * sizeof(float), hipMemcpyDeviceToHost));
+    return TWL_OK;
 }
 
 }  // extern "C"

@@ -163,6 +163,11 @@ int first_protein(Call &c, Ran &ran, int *grid, int *window)
         HIP_TRY(hipGetLastError());
         a.sim = (const float *)d->sim.p;
         a.sim_off = (const long long *)d->sim_off.p;
+        // what twl_dp_score_matrix reads back: host integers only
+        d->sim_last_off.assign((size_t)n_pairs, -1);
+        for (int32_t t = 0; t < n_run; ++t) d->sim_last_off[(size_t)c.order[t]] = off[(size_t)c.order[t]];
+        d->sim_last_len.assign(h_len, h_len + 2 * (size_t)n_pairs);
+        d->sim_last_corridor = sa.corridor;
     }
     switch (pl.first) {
     case ProtFirst::MtPresim: return launch_mt<22, 4, 1>(d, st, a, items, c.order, n_run, h_len, grid, window);
@@ -427,6 +432,7 @@ int run_device(Device *d, hipStream_t st, const twl_params *p, int32_t n_pairs, 
     d->fills.n = 0;
     d->last_err.clear();
     d->last_alnlen.clear();
+    d->sim_last_off.clear(); d->sim_last_len.clear(); d->sim_last_corridor = 0;      // (twl_dp_score_matrix: first_protein fills them in when it precomputes)
     d->pair_cells.assign((size_t)n_pairs, 0);
     if (n_pairs == 0) return TWL_OK;
 
